@@ -2,12 +2,25 @@
 """Hot-path benchmark: yolo-pose.cfg training step (zero_grad, forward, RegionLoss, backward, grad all-reduce, SGD) on
 synthetic 416x416 batches, 64 images per GPU (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` = images/s of the whole job (all ranks), max-over-ranks time of exactly K
-steps between barrier + synchronize pairs, inputs resident in HBM.  `roofline` is for the dominant kernel (the
+steps between barrier + synchronize pairs, inputs resident in HBM; `ms_per_step` = that time / K.  Every step starts
+from the same seeded weights, and the metric's workload runs the committed plan set cfg/bench_tune_cache.json (unless
+SSP_TUNE_CACHE names another): with the same arguments, each run computes the same step up to fp32 rounding.
+
+A plain run does only what that headline needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs)
+and the result line.  --dump-outputs DIR writes what the last timed step computed, as a caller of the step receives it:
+the head output, the loss, a fixed seeded sample of the updated parameters and of their gradients, the BatchNorm
+running statistics (DIR/<name>.npy, float32 / float64, about 35 MB).
+
+Everything else is measured with --full only: the oracle check of one step before timing (`verify`), the per-launch HIP
+event timers in the timed region and the further untimed passes behind the rooflines and `kernel_ms_per_step`, the
+multi-rank gradient check and `comm` diagnostics, the other configurations (`extra`) and `cpu_baseline`.
+
+With --full: `roofline` is for the dominant kernel (the
 implicit-GEMM conv kernel, forward launches): the FLOPs its MFMA pipe EXECUTED (a Winograd-plan layer counts its batched
 GEMMs, not the direct convolution) / the HIP-event time of those launches, against the fp32 MFMA peak (157.3 TFLOP/s,
 MI355X_MICROARCH.md), from HIP events inside the timed region (on every 5th step of it: `roofline.timed_steps` - carried by
@@ -266,6 +279,26 @@ def verify_step(model, crit, B, H, W, seed, exact=False):
     return ok, det
 
 
+def dump_outputs(out_dir, model, loss, head, sample=1 << 22):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the head output, the loss, the BatchNorm running
+    statistics, and of the updated parameters and their gradients (50.5 M floats each, in model.parameters() order and
+    logical NCHW order) the same `sample` positions, drawn with a fixed seed - about 35 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    if n > sample:
+        idx = torch.randint(0, n, (sample,), generator=torch.Generator().manual_seed(0)).sort().values.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    running = [b.detach().reshape(-1).float() for name, b in model.named_buffers() if name.endswith(('running_mean', 'running_var'))]
+    arrays = {'head': head, 'loss': loss.detach().reshape(1), 'params_sample': flat_p, 'grads_sample': flat_g,
+              'bn_running_stats': torch.cat(running)}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def extras(device, steps=5):
     """Driver-record lines for BASELINE configs 4 and 5 (not the metric): the multi-object cfg's training step and the
     inference path at valid.py's 672 x 672 operating point."""
@@ -434,7 +467,14 @@ def main():
                     help='for runs under rocprofv3: only the warm-up and the timed steps (no per-family breakdown pass, no '
                          'kernel-exclusive pass), so the trace holds nothing but real training steps')
     ap.add_argument('--opt', default='', help='kernel experiment knobs, name=value,... (ssp_set_option); default: none')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the oracle check, the rooflines / per-kernel breakdown, the multi-rank diagnostics, the other '
+                         'configurations and the CPU baseline (the --no-* / --timers / --profile-run options refine it)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -457,14 +497,18 @@ def main():
         sock.close()
         os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
         sys.stdout.flush()
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
-                                  '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        # a child process, not exec: this process has already opened the GPU runtime (device_count above)
+        import subprocess
+        rc = subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
+                              '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(rc)
     torch.cuda.set_device(local_rank)
     device = torch.device('cuda', local_rank)
 
     from singleshotpose_amd import _lib
     from singleshotpose_amd.darknet import Darknet
     from singleshotpose_amd.dist import GradReducer, init_distributed
+    from singleshotpose_amd.engine import weights_changed
     from singleshotpose_amd.optim import SGD
     from singleshotpose_amd.region_loss import RegionLoss
 
@@ -477,6 +521,18 @@ def main():
         name, val = kv.split('=')
         _lib.call('ssp_set_option', name.encode(), int(val))
 
+    if not os.environ.get('SSP_TUNE_CACHE') and (args.cfg, args.batch, args.size) == (ap.get_default('cfg'), 64, 416):
+        # the metric's workload runs a committed plan set (cfg/bench_tune_cache.json: what the autotuner timed on an MI355X
+        # for exactly this workload): timing-based choices differ from run to run in the last bits of their sums.  A copy,
+        # because the engine rewrites the file whenever it times a new shape.
+        import shutil
+        import tempfile
+        import atexit
+        tmp = tempfile.mkdtemp(prefix='ssp_bench_')
+        atexit.register(shutil.rmtree, tmp, True)
+        tc = os.path.join(tmp, 'tune_cache.json')
+        shutil.copy(os.path.join(ROOT, 'cfg', 'bench_tune_cache.json'), tc)
+        os.environ['SSP_TUNE_CACHE'] = tc
     torch.manual_seed(0)                       # identical initial weights on every rank
     model = Darknet(args.cfg).to(device).train()
     crit = RegionLoss()
@@ -491,14 +547,33 @@ def main():
         from singleshotpose_amd.dist import sync_plans
         sync_plans(model)        # every rank runs rank 0's plan set (same shape on every rank here: the broadcasts pair up)
     x, tgt = synthetic_batch(B, H, W, 1000 + rank, device)
+    last_out = [None]
+    # Every step trains from the SAME seeded weights: the dynamics of this randomly initialised network amplify the last-bit
+    # differences of the filter gradients' fp32 atomics (~1e-6) to O(1) within ~20 SGD steps, so with evolving weights the
+    # step a run ends on differs from run to run.  The optimizer's flat parameter buffer (it exists after the first
+    # opt.step) is reset to the initial weights before each later step - one 202 MB device copy; momentum and the BatchNorm
+    # running statistics carry over (they do not feed back into the gradients).
+    init_params = [p.detach().clone() for p in model.parameters()]
+    init_flat = [None]
 
     def step():
+        if init_flat[0] is None and opt._flat_p is not None:
+            with torch.no_grad():
+                for p, p0 in zip(model.parameters(), init_params):
+                    p.copy_(p0)
+            init_flat[0] = opt._flat_p.clone()
+            init_params.clear()
+        elif init_flat[0] is not None:
+            opt._flat_p.copy_(init_flat[0])
+        if init_flat[0] is not None:
+            weights_changed()                   # raw parameter memory changed: packed-filter caches must not be reused
         opt.zero_grad(set_to_none=True)
         out = model(x)
         loss = crit(out, tgt, 20)               # epoch 20 > pretrain: confidence term active
         loss.backward()
         reducer.all_reduce()                    # RCCL SUM over ranks (no-op for world 1)
         opt.step()
+        last_out[0] = out.detach()
         return loss
 
     def barrier():
@@ -507,7 +582,7 @@ def main():
         torch.cuda.synchronize()
 
     grad_check = None
-    if dist_on and os.environ.get('SSP_BENCH_SKIP_GRAD_CHECK') != '1':
+    if args.full and dist_on and os.environ.get('SSP_BENCH_SKIP_GRAD_CHECK') != '1':
         # SURVEY.md 8(d) config 3, untimed: every rank runs the SAME batch (same seed, same initial weights), once with the
         # reducer standing aside and once through it - the reduced flat gradient must be world x the local one (<= 1e-5 of
         # its range; the filter-gradient kernels' fp32 atomics make two evaluations differ in the last bits)
@@ -543,7 +618,7 @@ def main():
             grad_check = {"error": repr(e)}
 
     verified, verify_detail = None, None
-    if world == 1 and not args.no_verify:
+    if args.full and world == 1 and not args.no_verify:
         verified, verify_detail = verify_step(model, crit, B, H, W, 1000 + rank, exact=args.verify_exact)
     for _ in range(args.warmup):
         step()
@@ -568,7 +643,8 @@ def main():
     # with the Winograd and on-chip families).  On every step they cost 0.37 ms of the step (same box: 25.20 / 25.22 ms with,
     # 24.82 / 24.86 ms without them; a plain loop without the profiler hooks 24.69 ms) - an instrument should not move the
     # number it sits next to.  `roofline.timed_steps` says how many steps the per-launch averages come from.
-    timer_mask = {'conv': (1 << 0) | (1 << 9) | (1 << 12), 'all': -1, 'none': 0}[args.timers]
+    # (a plain run carries none: nothing in its result line reads them)
+    timer_mask = {'conv': (1 << 0) | (1 << 9) | (1 << 12), 'all': -1, 'none': 0}[args.timers] if args.full else 0
     n_timed = 0
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -580,6 +656,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     _lib.call('ssp_prof_enable', 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, last_out[0])
     n_timed = max(n_timed, 1)
     ms, work, cnt = collect()
     # Per-family breakdown (kernel_ms_per_step, roofline_bwd): a separate, untimed pass of the same steps with every
@@ -587,11 +665,11 @@ def main():
     # Collected step by step and reduced with the MEDIAN over steps: one stretched event (a clock ramp, another process
     # on the host) would otherwise add milliseconds to a family's mean.
     nb = min(args.steps, 5)
+    no_passes = args.profile_run or not args.full
     per_step = []
-    if args.profile_run:
-        per_step = [collect()]
-        per_step[0] = ([0.0] * nk, [0.0] * nk, [0] * nk)
-    for _ in range(0 if args.profile_run else nb):
+    if no_passes:
+        per_step = [([0.0] * nk, [0.0] * nk, [0] * nk)]
+    for _ in range(0 if no_passes else nb):
         _lib.call('ssp_prof_enable', -1)
         loss = step()
         barrier()
@@ -606,8 +684,8 @@ def main():
     # each other's events: that pair is `roofline_bwd`).  Untimed, after the measurement; same operands, same plans.
     for plan in model._plans.values():
         plan.serial_backward = True
-    ex_step = [([0.0] * nk, [0.0] * nk, [0] * nk)] if args.profile_run else []
-    for _ in range(0 if args.profile_run else 3):
+    ex_step = [([0.0] * nk, [0.0] * nk, [0] * nk)] if no_passes else []
+    for _ in range(0 if no_passes else 3):
         _lib.call('ssp_prof_enable', (1 << 1) | (1 << 2) | (1 << 10) | (1 << 11) | (1 << 13) | (1 << 14))      # dgrad, wgrad, their Winograd passes, the on-chip forms
         loss = step()
         barrier()
@@ -617,7 +695,7 @@ def main():
         plan.serial_backward = False
     ex = {k: (float(np.median([p[0][k] for p in ex_step])), float(np.median([p[1][k] for p in ex_step])),
               float(np.median([p[2][k] for p in ex_step]))) for k in (1, 2, 10, 11, 13, 14)}
-    if dist_on:
+    if args.full and dist_on:
         # communication diagnostics (untimed): per-bucket all-reduce issue -> done times and the exposed tail of one step
         reducer.profile = True
         loss = step()
@@ -635,8 +713,31 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
+    images_per_s = global_batch * args.steps / dt
+    headline = {
+        "metric": "images/sec (fwd+bwd) yolo-pose 416x416 bs=64/GPU",
+        "value": round(images_per_s, 2),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "cfg/yolo-pose.cfg train step (zero_grad+fwd+RegionLoss+bwd+grad all-reduce+SGD), "
+                               "%dx%d, batch %d/GPU, random-init weights, 1 label/image" % (H, W, B),
+                   "global_batch": global_batch, "parallelism": "dp%d" % world},
+        # headline fraction of the step: ALL conv FLOPs of fwd+bwd (87.673 GFLOP per image) over the whole step's
+        # wall time - BatchNorm / activation / loss / optimizer time included in the denominator
+        "step_conv_effective_flop_frac_of_peak": round(images_per_s / world * 87.673e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
+    }
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        res = dict(headline, final_loss=final_loss, head_budget=_budget_record(model))
+    elif rank == 0:
         kinds = _lib.PROF_KINDS
         prof = {kinds[k]: {"ms_per_step": bms[k] / nb, "launches_per_step": bcnt[k] / nb,
                            "work_per_step": bwork[k] / nb} for k in range(nk)}
@@ -652,7 +753,6 @@ def main():
         bwd_ms = max(bms[1] + bms[13], bms[2] + bms[14])
         bwd_tf = (bwork[1] + bwork[2] + bwork[13] + bwork[14]) / (bwd_ms * 1e-3) / 1e12 if bwd_ms > 0 else 0.0
         traffic, traffic_src = forward_traffic_per_launch()
-        images_per_s = global_batch * args.steps / dt
 
         # FLOP accounting.  ALGORITHMIC = direct convolution, 2*M*Cout*k*k*Cin (what images/s converts to).
         # EXECUTED = what the MFMA pipe really issued: a layer the autotuner runs in the Winograd F(n x n, 3x3) domain
@@ -743,27 +843,9 @@ def main():
         hb_ms = sum(h["ms_per_step"] for h in hb)
         hb_bytes = sum(h["bytes_per_step"] for h in hb)
         step_exec = sum(exe.values()) + sum(exe_oc.values()) + 4 * 2.0 * B * H * W * 32 * 27
-        res = {
-            "metric": "images/sec (fwd+bwd) yolo-pose 416x416 bs=64/GPU",
-            "value": round(images_per_s, 2),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "cfg/yolo-pose.cfg train step (zero_grad+fwd+RegionLoss+bwd+grad all-reduce+SGD), "
-                                   "%dx%d, batch %d/GPU, random-init weights, 1 label/image" % (H, W, B),
-                       "global_batch": global_batch, "parallelism": "dp%d" % world},
-            # headline fraction of the step: ALL conv FLOPs of fwd+bwd (87.673 GFLOP per image) over the whole step's
-            # wall time - BatchNorm / activation / loss / optimizer time included in the denominator
-            "step_conv_effective_flop_frac_of_peak": round(images_per_s / world * 87.673e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
-            # ... and the FLOPs the MFMA pipe really issued in a step (Winograd layers counted as their GEMMs; the first
-            # block's four recomputing passes included) over the same wall time: whole-step pipe utilisation
+        res = dict(headline, **{
+            # the FLOPs the MFMA pipe really issued in a step (Winograd layers counted as their GEMMs; the first block's
+            # four recomputing passes included) over the step's wall time: whole-step pipe utilisation
             "step_mfma_executed_frac_of_peak": round(step_exec / (dt / args.steps) / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
             "roofline": dict(family("fwd", IGEMM % (0, 0, 0, 0, 0) + "; the forward launch units of layers 2-30 (the first block's "
                                     "two passes are first_block_kernel<0|1>: kernel_ms_per_step.first_block_fwd)",
@@ -833,7 +915,7 @@ def main():
             # candidate measured on the first batch, the layers that were moved to a more accurate family to keep the
             # budget, and the launch time that cost
             "head_budget": _budget_record(model),
-        }
+        })
         if dist_on:
             res["comm"] = comm
         if world == 1 and not args.no_extras:

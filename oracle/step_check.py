@@ -221,10 +221,12 @@ def check_train_step(model, crit, x_cpu, tgt, epoch, loss_kwargs=None, frozen_ba
         mine = seq[0].weight.grad.cpu()
         err = _rel(mine, e['weight'].grad)
         first_conv = ind == min(i for i, e_ in enumerate(st_b) if e_ is not None)
-        if (err > 1e-4 or first_conv) and ind in tape:
+        if (err > 5e-5 or first_conv) and ind in tape:
             # An ill-conditioned filter gradient (the first layer's is sum dx * image with sum dx = 0 exactly and an
             # all-positive image: the terms cancel ~1e3 : 1 at B = 64) - the oracle's OWN fp32 accumulation (oneDNN) sits
-            # >1e-4 from the exact sum of its own operands.  Re-evaluate the oracle's gradient from the very same
+            # >1e-4 from the exact sum of its own operands.  How far depends on the host CPU's oneDNN kernels (layer 0 at
+            # 352 x 352, B = 64: 2.3e-4 on one host, 2.2e-3 on another), so the trigger sits below every gradient bar of
+            # the callers (tests 7e-5, bench.py 1e-4).  Re-evaluate the oracle's gradient from the very same
             # (input, dL/d raw) tensors in float64 and compare against that: a tighter oracle, not a looser bar.  The first
             # layer's filter gradient is ALWAYS judged this way (round 5): against the fp32 oracle its "error" read 3e-5 ...
             # 1e-4 from shape to shape - the oracle's own rounding; against the float64 sum the product sits at ~1e-5.

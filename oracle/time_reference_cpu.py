@@ -4,8 +4,8 @@
 BASELINE INFRASTRUCTURE (last row), always run as its OWN PROCESS: it redirects torch.cuda.* to
 the CPU, which must never happen inside a process that drives the GPU.  The modules are the reference's unmodified
 darknet.py / utils.py / cfg.py and region_loss.py with the three mechanical torch >= 0.5 patches of SURVEY.md section
-8(c) applied in memory (oracle/gen_golden.load_patched), taken from /root/reference when it is mounted, else from
-oracle/_ref/modules.zip (oracle/stage_reference.py; the GPU box).  One step = what train.py:83-103 does per batch:
+8(c) applied in memory (oracle/gen_golden.load_patched), taken from oracle/_ref/modules.zip (staged by
+oracle/stage_reference.py at build time).  One step = what train.py:83-103 does per batch:
 Darknet.forward (train mode), RegionLoss.forward (epoch 20), loss.backward().
 
     python oracle/time_reference_cpu.py CFG BATCH SIZE THREADS[,THREADS...] [REPEATS]   -> one JSON line
@@ -24,8 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def reference_dir():
-    if os.path.isfile('/root/reference/darknet.py') and os.environ.get('SSP_REF_FROM_ZIP') != '1':
-        return '/root/reference', 'in place'
     z = os.path.join(ROOT, 'oracle', '_ref', 'modules.zip')
     if not os.path.isfile(z):
         return None, None
@@ -40,7 +38,7 @@ def main(argv):
     repeats = int(argv[4]) if len(argv) > 4 else 1
     ref, how = reference_dir()
     if ref is None:
-        print(json.dumps({"error": "no reference modules (neither /root/reference nor oracle/_ref/modules.zip)"}))
+        print(json.dumps({"error": "no reference modules (oracle/_ref/modules.zip is not staged)"}))
         return 2
     import numpy as np
     import torch

@@ -1,8 +1,8 @@
 """The drop-in, executed: the reference's UNMODIFIED valid.py and train.py run against this package on the MI355X.
 
 north_star: "keep the reference's plugin surface ... so train.py / valid.py drop in unchanged".  The driver scripts are
-the reference's own files, byte for byte (staged by __graft_entry__.build() into the git-ignored oracle/_ref/callers.zip
-because the GPU box has no /root/reference; or taken from /root/reference when it is there).  They run as subprocesses
+the reference's own files, byte for byte (staged by __graft_entry__.build() into the git-ignored oracle/_ref/callers.zip;
+the tests read nothing outside the repository tree).  They run as subprocesses
 with PYTHONPATH=<repo>:<repo>/dropin - the module-name shims (cfg, darknet, region_loss, utils, cv2 stand-in,
 torchvision's Compose / ToTensor) - over the synthetic LINEMOD-shaped fixture of tests/fixture_linemod.py, and what they
 print is compared with tests/golden/dropin_*.json: the same scripts run on the CPU reference in the build container
@@ -32,14 +32,8 @@ def _callers_dir(tmp_path, names=CALLERS, sub='reference_callers'):
     """A directory holding ONLY the driver scripts (and dataset.py / image.py / MeshPly.py): `python <dir>/valid.py`
     puts <dir> first on sys.path, and darknet / region_loss / utils / cfg must resolve to dropin/, not to the reference.
     `names` without dataset.py / image.py: those two resolve to dropin/ as well (the GPU augmentation)."""
-    import shutil
     dst = str(tmp_path / sub)
     os.makedirs(dst, exist_ok=True)
-    ref = '/root/reference'
-    if all(os.path.isfile(os.path.join(ref, n)) for n in names):
-        for n in names:
-            shutil.copy(os.path.join(ref, n), os.path.join(dst, n))
-        return dst
     z = os.path.join(ROOT, 'oracle', '_ref', 'callers.zip')
     if not os.path.isfile(z):
         pytest.skip("the reference's driver scripts are not staged (oracle/_ref/callers.zip: run __graft_entry__.build() "
@@ -164,7 +158,7 @@ def test_dropin_dataset_epoch_is_the_reference_epoch_byte_for_byte(tmp_path, nam
             want = np.array([[float.fromhex(v) for v in r] for r in b['labels'][s]]).reshape(-1, 21)
             assert np.array_equal(rows[s, :len(want)], want) and not rows[s, len(want):].any()
     z = os.path.join(ROOT, 'oracle', '_ref', 'callers.zip')
-    if os.path.isfile(z) or os.path.isdir('/root/reference'):
+    if os.path.isfile(z):
         ref = _callers_dir(tmp_path, ('dataset.py', 'image.py'), 'reference_dataset')
         out_ref = str(tmp_path / 'reference.npz')
         _run([sys.executable, tool, root, out_ref, '--cpu'] + args, str(tmp_path), first=[ref])
@@ -197,7 +191,7 @@ def test_dropin_image_module_per_sample_functions_equal_the_reference(tmp_path):
     distort_image give the reference's bytes and labels for the same seed (non-square network shape, a background of
     another aspect ratio)."""
     z = os.path.join(ROOT, 'oracle', '_ref', 'callers.zip')
-    if not (os.path.isfile(z) or os.path.isdir('/root/reference')):
+    if not os.path.isfile(z):
         pytest.skip("the reference's image.py is not staged (oracle/_ref/callers.zip)")
     root = str(tmp_path / 'fixture')
     fx.make(root, n_train=4, n_test=1)
@@ -263,15 +257,8 @@ def _multi_callers_dir(tmp_path):
     in a directory of their own: `python <dir>/train_multi.py` puts <dir> first on sys.path, so dataset_multi / image_multi
     (the PIL pipeline, out of this repo's scope) are the reference's, while darknet_multi / region_loss_multi / utils_multi /
     cfg resolve to dropin/."""
-    import shutil
     dst = str(tmp_path / 'multi_callers')
     os.makedirs(dst, exist_ok=True)
-    ref = '/root/reference'
-    if all(os.path.isfile(os.path.join(ref, 'multi_obj_pose_estimation', n)) for n in MULTI_CALLERS):
-        for n in MULTI_CALLERS:
-            shutil.copy(os.path.join(ref, 'multi_obj_pose_estimation', n), os.path.join(dst, n))
-        shutil.copy(os.path.join(ref, 'MeshPly.py'), os.path.join(dst, 'MeshPly.py'))
-        return dst
     z = os.path.join(ROOT, 'oracle', '_ref', 'callers.zip')
     if not os.path.isfile(z) or 'multi_obj_pose_estimation/train_multi.py' not in zipfile.ZipFile(z).namelist():
         pytest.skip("the reference's multi-object driver scripts are not staged (oracle/_ref/callers.zip: run "

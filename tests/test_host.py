@@ -361,7 +361,7 @@ def test_reference_cpu_baseline_harness_runs_from_the_staged_archive():
     assert 'darknet.py' in prov and 'sha1' in prov
     out = subprocess.run([sys.executable, os.path.join(root, 'oracle', 'time_reference_cpu.py'),
                           os.path.join(root, 'cfg', 'yolo-pose.cfg'), '1', '96', '4', '1'], capture_output=True, text=True,
-                         timeout=600, env=dict(os.environ, SSP_REF_FROM_ZIP='1', CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES=''))
+                         timeout=600, env=dict(os.environ, CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES=''))
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     assert rec['params'] == 50547764 and rec['seconds_per_step']['4'] > 0 and 'modules.zip' in rec['modules']
 

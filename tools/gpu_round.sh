@@ -8,7 +8,7 @@
 #   tests        the whole `pytest -m gpu` suite              (PYTEST_PATHS="tests/test_x.py::test_y ..." narrows it, PYTEST_ARGS adds
 #                flags, PYTEST_SECONDS bounds it)
 #   smoke        __graft_entry__.smoke()
-#   bench        the driver's command: python bench.py --steps 20 --warmup 5       (BENCH_ARGS adds flags)
+#   bench        the full record: python bench.py --full --steps 20 --warmup 5     (BENCH_ARGS adds flags)
 #   benchq       the same without extras / CPU baseline (verify stays on)          (BENCH_ARGS adds flags)
 #   ab           whole-step A/B on this box, two interleaved rounds: AB_CFGS="-;@acc_chunk=0;SSP_WINOGRAD=0"  (BENCH_ARGS adds flags)
 #                (a cfg is "-" = defaults, VAR=value environment settings and / or @name=value,... = bench.py --opt)
@@ -66,10 +66,10 @@ for STAGE in "$@"; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1
       tail -2 $OUT/smoke_$TAG.log ;;
     bench)
-      timeout 1500 python bench.py --steps 20 --warmup 5 $BENCH_ARGS > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+      timeout 1500 python bench.py --full --steps 20 --warmup 5 $BENCH_ARGS > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
       tail -3 $OUT/bench_$TAG.err; bench_line $OUT/bench_$TAG.json ;;
     benchq)
-      timeout 900 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline $BENCH_ARGS > $OUT/benchq_$TAG.json 2> $OUT/benchq_$TAG.err
+      timeout 900 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline $BENCH_ARGS > $OUT/benchq_$TAG.json 2> $OUT/benchq_$TAG.err
       tail -3 $OUT/benchq_$TAG.err; bench_line $OUT/benchq_$TAG.json ;;
     ab)
       IFS=';' read -ra CFGS <<< "${AB_CFGS:--}"
@@ -79,14 +79,14 @@ for STAGE in "$@"; do
           for tok in $o; do
             case "$tok" in -) ;; @*) a="--opt ${tok#@}" ;; *) e="$e $tok" ;; esac
           done
-          env $e timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-verify --no-extras $BENCH_ARGS $a 2>$OUT/ab_$TAG.err | tail -1 | \
+          env $e timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-verify --no-extras $BENCH_ARGS $a 2>$OUT/ab_$TAG.err | tail -1 | \
             python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-40s %8.2f img/s %7.3f ms  fwd %.1f TF bwd %.1f TF' % ('$o', d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline_bwd']['achieved']), d['kernel_ms_per_step'])" | tee -a $OUT/ab_$TAG.log
         done
       done ;;
     profile)
       export SSP_TUNE_VERIFY=0      # choices come from the bench stage's cache, verified there: no verify launches in the trace
       (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o prof -- \
-        python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-extras --profile-run $BENCH_ARGS > $OUT/prof_$TAG.log 2>&1)
+        python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-extras --profile-run $BENCH_ARGS > $OUT/prof_$TAG.log 2>&1)
       unset SSP_TUNE_VERIFY
       F=$(find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1)
       [ -n "$F" ] && cp "$F" $OUT/kernel_stats_$TAG.csv && head -24 "$F" | cut -c1-170
@@ -99,7 +99,7 @@ for STAGE in "$@"; do
       mkdir -p $OUT/pmc_traffic_$TAG
       for C in FETCH_SIZE WRITE_SIZE; do
         (cd /tmp && timeout 240 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_traffic_$TAG/$C -o p -- \
-          python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-verify --no-extras --profile-run $BENCH_ARGS > $OUT/pmc_traffic_$TAG/$C.log 2>&1)
+          python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-verify --no-extras --profile-run $BENCH_ARGS > $OUT/pmc_traffic_$TAG/$C.log 2>&1)
       done
       unset SSP_TUNE_VERIFY
       python tools/traffic_summary.py $OUT/pmc_traffic_$TAG $OUT/traffic_$TAG.json | head -40
