@@ -264,6 +264,32 @@ int ssp_maxpool_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, 
 int ssp_maxpool_bwd(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W,
                     int accumulate, void* stream);
 
+/* ---- generic Darknet blocks (csrc/generic_blocks.hip): fp32 NHWC [pixels][ld] maps, ld % 4 == 0; backward passes write
+ * (accumulate = 0) or add (accumulate = 1) into the input gradient ------------------------------------------------ */
+/* MaxPoolStride1 (darknet.py:8-14, chosen at :168-176 when stride == 1): out = max_pool2d(pad(x, (0,1,0,1), 'replicate'),
+ * 2, stride=1), H x W -> H x W (the cfg's size is ignored); C % 4 == 0.  Backward recomputes the winner from x (first
+ * maximum in row-then-column order); a winner on the pad folds onto the edge pixel */
+int ssp_maxpool_s1_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, void* stream);
+int ssp_maxpool_s1_bwd(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W,
+                       int accumulate, void* stream);
+/* shortcut (darknet.py:107-118, :210-214): out = act(a + b) over M pixels, slope 1 = linear, 0.1 = leaky, 0 = relu; C % 4 == 0.
+ * Backward: g' = g * act'(out) (from out > 0, as in-place leaky_relu / relu); da (+)= g', db (+)= g'.  da == db (from = -1:
+ * both summands are one map) adds 2 g' and needs ldda == lddb, acc_a == acc_b */
+int ssp_shortcut_fwd(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int C, int64_t M, float slope,
+                     void* stream);
+int ssp_shortcut_bwd(const float* g, int ldg, const float* out, int ldo, float* da, int ldda, int acc_a, float* db, int lddb,
+                     int acc_b, int C, int64_t M, float slope, void* stream);
+/* GlobalAvgPool2d (darknet.py:37-47, :177-180): (B,H,W,C) -> out[b][c] (B rows of ldo), fixed summation order
+ * (deterministic); backward dx[b][p][c] (+)= g[b][c] / (H * W); C % 4 == 0 */
+int ssp_avgpool_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, void* stream);
+int ssp_avgpool_bwd(const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W, int accumulate, void* stream);
+/* nn.Softmax() (darknet.py:181-184; implicit dim = 1): softmax over the C channels of each of M rows (B samples of a 2-D
+ * input or B*H*W pixels of an NHWC map), row maximum subtracted before exp; channels >= C are neither read nor written.
+ * Backward: dx (+)= y * (g - sum_c g * y) */
+int ssp_softmax_fwd(const float* x, int ldx, float* y, int ldy, int C, int64_t M, void* stream);
+int ssp_softmax_bwd(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M, int accumulate,
+                    void* stream);
+
 /* ---- RegionLoss (region_loss.py:9-175, region_loss_multi.py:9-189, utils.py:138-187) ----------------------- */
 /* out, grad: (nB, nA*(2K+1+nC), nH, nW) NCHW contiguous; target: (nB, 50*(2K+3)) float or double on the device;
  * partials: nB*8 floats; stats[8] = {loss_x, loss_y, loss_conf, loss_cls, total, nGT, nCorrect, nProposals}. */

@@ -77,6 +77,14 @@ _SIGS = {
     "ssp_copy_channels": [P, I, P, I, I, L, I, P],
     "ssp_maxpool_fwd": [P, I, P, I, I, I, I, I, P],
     "ssp_maxpool_bwd": [P, I, P, I, P, I, I, I, I, I, I, P],
+    "ssp_maxpool_s1_fwd": [P, I, P, I, I, I, I, I, P],
+    "ssp_maxpool_s1_bwd": [P, I, P, I, P, I, I, I, I, I, I, P],
+    "ssp_shortcut_fwd": [P, I, P, I, P, I, I, L, F, P],
+    "ssp_shortcut_bwd": [P, I, P, I, P, I, I, P, I, I, I, L, F, P],
+    "ssp_avgpool_fwd": [P, I, P, I, I, I, I, I, P],
+    "ssp_avgpool_bwd": [P, I, P, I, I, I, I, I, I, P],
+    "ssp_softmax_fwd": [P, I, P, I, I, L, P],
+    "ssp_softmax_bwd": [P, I, P, I, P, I, I, L, I, P],
     "ssp_region_loss": [P, P, I, P, P, P, I, I, I, I, I, I, F, F, F, F, F, I, I, P, I, P],
     "ssp_region_decode_argmax": [P, P, I, I, I, I, I, I, I, P],
     "ssp_region_decode_all": [P, P, I, I, I, I, I, I, P],

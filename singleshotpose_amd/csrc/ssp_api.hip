@@ -77,6 +77,20 @@ int ssp_copy_channels_launch(const float* src, int lds_, float* dst, int ldd, in
 int ssp_maxpool_fwd_launch(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, hipStream_t stream);
 int ssp_maxpool_bwd_launch(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H,
                            int W, int accumulate, hipStream_t stream);
+int ssp_maxpool_s1_fwd_launch(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W,
+                              hipStream_t stream);
+int ssp_maxpool_s1_bwd_launch(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H,
+                              int W, int accumulate, hipStream_t stream);
+int ssp_shortcut_fwd_launch(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int C, int64_t M,
+                            float slope, hipStream_t stream);
+int ssp_shortcut_bwd_launch(const float* g, int ldg, const float* out, int ldo, float* da, int ldda, int acc_a, float* db,
+                            int lddb, int acc_b, int C, int64_t M, float slope, hipStream_t stream);
+int ssp_avgpool_fwd_launch(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, hipStream_t stream);
+int ssp_avgpool_bwd_launch(const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W, int accumulate,
+                           hipStream_t stream);
+int ssp_softmax_fwd_launch(const float* x, int ldx, float* y, int ldy, int C, int64_t M, hipStream_t stream);
+int ssp_softmax_bwd_launch(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M,
+                           int accumulate, hipStream_t stream);
 int ssp_region_loss_launch(const float* out, const void* target, int target_is_f64, float* grad, float* partials,
                            float* stats, int nB, int nA, int nC, int nH, int nW, int num_keypoints,
                            float noobject_scale, float object_scale, float coord_scale, float class_scale, float thresh,
@@ -372,6 +386,34 @@ int ssp_maxpool_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, 
 int ssp_maxpool_bwd(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W,
                     int accumulate, void* stream) {
   return ssp_maxpool_bwd_launch(x, ldx, g, ldg, dx, lddx, C, B, H, W, accumulate, (hipStream_t)stream);
+}
+int ssp_maxpool_s1_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, void* stream) {
+  return ssp_maxpool_s1_fwd_launch(x, ldx, out, ldo, C, B, H, W, (hipStream_t)stream);
+}
+int ssp_maxpool_s1_bwd(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W,
+                       int accumulate, void* stream) {
+  return ssp_maxpool_s1_bwd_launch(x, ldx, g, ldg, dx, lddx, C, B, H, W, accumulate, (hipStream_t)stream);
+}
+int ssp_shortcut_fwd(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int C, int64_t M, float slope,
+                     void* stream) {
+  return ssp_shortcut_fwd_launch(a, lda, b, ldb, out, ldo, C, M, slope, (hipStream_t)stream);
+}
+int ssp_shortcut_bwd(const float* g, int ldg, const float* out, int ldo, float* da, int ldda, int acc_a, float* db, int lddb,
+                     int acc_b, int C, int64_t M, float slope, void* stream) {
+  return ssp_shortcut_bwd_launch(g, ldg, out, ldo, da, ldda, acc_a, db, lddb, acc_b, C, M, slope, (hipStream_t)stream);
+}
+int ssp_avgpool_fwd(const float* x, int ldx, float* out, int ldo, int C, int B, int H, int W, void* stream) {
+  return ssp_avgpool_fwd_launch(x, ldx, out, ldo, C, B, H, W, (hipStream_t)stream);
+}
+int ssp_avgpool_bwd(const float* g, int ldg, float* dx, int lddx, int C, int B, int H, int W, int accumulate, void* stream) {
+  return ssp_avgpool_bwd_launch(g, ldg, dx, lddx, C, B, H, W, accumulate, (hipStream_t)stream);
+}
+int ssp_softmax_fwd(const float* x, int ldx, float* y, int ldy, int C, int64_t M, void* stream) {
+  return ssp_softmax_fwd_launch(x, ldx, y, ldy, C, M, (hipStream_t)stream);
+}
+int ssp_softmax_bwd(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M, int accumulate,
+                    void* stream) {
+  return ssp_softmax_bwd_launch(y, ldy, g, ldg, dx, lddx, C, M, accumulate, (hipStream_t)stream);
 }
 
 int ssp_region_loss(const float* out, const void* target, int target_is_f64, float* grad, float* partials,

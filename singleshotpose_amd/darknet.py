@@ -164,8 +164,16 @@ class Darknet(nn.Module):
                 out_filters.append(prev_filters)
                 models.append(EmptyModule())
             elif t == 'connected':
+                # darknet.py:215-229: the activation rides in an nn.Sequential (state_dict keys models.N.0.*); linear is a
+                # bare nn.Linear (models.N.*).  Executed by the plan as a 1x1 convolution of the (B, Cin) input.
                 filters = int(block['output'])
-                models.append(nn.Linear(prev_filters, filters))
+                act = block['activation']
+                if act == 'leaky':
+                    models.append(nn.Sequential(nn.Linear(prev_filters, filters), nn.LeakyReLU(0.1, inplace=True)))
+                elif act == 'relu':
+                    models.append(nn.Sequential(nn.Linear(prev_filters, filters), nn.ReLU(inplace=True)))
+                else:
+                    models.append(nn.Linear(prev_filters, filters))
                 prev_filters = filters
                 out_filters.append(prev_filters)
             elif t == 'region':
@@ -242,7 +250,7 @@ class Darknet(nn.Module):
     def _params(self):
         ps = []
         for m in self.models:
-            if isinstance(m, nn.Sequential):
+            if isinstance(m, (nn.Sequential, nn.Linear)):     # conv / connected blocks (a linear connected is a bare Linear)
                 for p in m.parameters():
                     ps.append(p)
         return ps
@@ -309,7 +317,8 @@ class Darknet(nn.Module):
                 else:
                     start = load_conv(buf, start, model[0])
             elif t == 'connected':
-                start = load_fc(buf, start, self.models[ind])
+                model = self.models[ind]
+                start = load_fc(buf, start, model[0] if isinstance(model, nn.Sequential) else model)
         # .data.copy_ (cfg.py's loaders, as the reference's) does not bump the autograd version counters the plans key
         # their cached filter packs / inference-mode BN constants on: invalidate them explicitly.  (Code that mutates
         # parameters through `.data` itself should call singleshotpose_amd.engine.weights_changed() too.)
@@ -343,7 +352,10 @@ class Darknet(nn.Module):
                     else:
                         save_conv(fp, model[0])
                 elif block['type'] == 'connected':
-                    save_fc(fp, self.models[ind])
+                    # bias then weight of the Linear - the format load_fc reads.  (The reference's branch, darknet.py:370-375,
+                    # names an undefined `fc` and swaps the two cases: it cannot save a connected block at all.)
+                    model = self.models[ind]
+                    save_fc(fp, model[0] if isinstance(model, nn.Sequential) else model)
 
 
 class DarknetMulti(Darknet):

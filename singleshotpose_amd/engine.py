@@ -9,6 +9,9 @@ Forward per conv block (darknet.py:145-167):
     -> ssp_bn_fwd_finalize (train) | ssp_bn_eval_prepare (eval) -> ssp_bn_act_fwd (BN + leaky [+ fused 2x2 max-pool])
 A max-pool block is fused into the preceding conv block when nothing else consumes the un-pooled map.
 route = alias or ssp_copy_channels into a concat buffer; reorg = ssp_reorg.
+The other Darknet blocks (darknet.py:8-47, :107-118, :168-229) run on csrc/generic_blocks.hip: stride-1 max-pool, shortcut,
+global average pool, softmax over channels; a connected block is planned as a 1x1 convolution of its (B, Cin) input on a 1x1
+map (M = B rows: the conv kernels, bias and activation path of a non-BN conv block).
 
 Backward mirrors it in reverse: ssp_bn_act_bwd (in place over the raw conv output) -> ssp_conv_wgrad ->
 ssp_unpack_grad, and ssp_conv_dgrad into the producer's gradient buffer (accumulating when a map has two consumers).
@@ -149,6 +152,8 @@ def _is_packed(wt, cinp):
     """True when the (Cout,Cin,kh,kw) parameter is stored channels-last, i.e. [Cout][kh][kw][Cin] in memory with no channel
     padding needed: that is the forward operand layout and the layout the filter gradient is accumulated in, so the
     kernels read / write the parameter (and its gradient) in place."""
+    if wt.dim() == 2:      # nn.Linear weight (Cout, Cin): the same bytes as a channels-last (Cout, Cin, 1, 1) filter
+        return wt.size(1) == cinp and wt.is_contiguous()
     return wt.size(1) == cinp and wt.permute(0, 2, 3, 1).is_contiguous()
 
 
@@ -233,12 +238,19 @@ class Plan(object):
         consumers = [[] for _ in range(nl)]
         for ind, block in enumerate(blocks[1:]):
             t = block['type']
-            if t in ('convolutional', 'maxpool', 'reorg'):
+            if t in ('convolutional', 'maxpool', 'reorg', 'avgpool', 'softmax', 'connected'):
                 if ind > 0:
                     consumers[ind - 1].append(ind)
             elif t == 'route':
                 for l in resolve_layers(block['layers'], ind):
                     consumers[l].append(ind)
+            elif t == 'shortcut':
+                # reads `from` and ind-1 (the same map twice for from = -1): a shortcut source has two consumers, which keeps
+                # it out of the single-consumer fusions (pool into the producing block, BN-backward sums into a dgrad)
+                if ind == 0:
+                    raise NotImplementedError("shortcut as the first block (it needs two earlier layers)")
+                consumers[resolve_layers(block['from'], ind)[0]].append(ind)
+                consumers[ind - 1].append(ind)
             elif t in ('region', 'cost'):
                 pass
             else:
@@ -258,19 +270,36 @@ class Plan(object):
         self.convs = {}      # layer index -> _ConvSpec
         self.fused_pool = set()   # maxpool layers folded into the preceding conv block
         self.acts = [None] * nl   # forward outputs
+        self.flat = [False] * nl  # layers whose output is 2-D (B, C) in the reference: avgpool, connected, softmax of those
         self.ops_fwd = []
         wsz = dsz = 0
         prev = self.input_act
+        prev_flat = False
         for ind, block in enumerate(blocks[1:]):
             t = block['type']
             w, h, c = self.shapes[ind]
-            if t == 'convolutional':
-                k, s = int(block['size']), int(block['stride'])
-                if s != 1 or k not in (1, 3) or (k == 3 and not int(block['pad'])):
-                    raise NotImplementedError("conv size=%d stride=%d pad=%s is outside the yolo-pose hot path" % (k, s, block['pad']))
+            zeros_or_empty = torch.empty if _pad4(c) == c else torch.zeros     # padding channels stay zero
+            if t in ('convolutional', 'connected'):
+                if t == 'convolutional':
+                    k, s = int(block['size']), int(block['stride'])
+                    if s != 1 or k not in (1, 3) or (k == 3 and not int(block['pad'])):
+                        raise NotImplementedError("conv size=%d stride=%d pad=%s is outside the yolo-pose hot path" % (k, s, block['pad']))
+                    bn = int(block['batch_normalize']) != 0
+                    seq = net.models[ind]
+                    conv, bnm = seq[0], (seq[1] if bn else None)
+                else:
+                    # connected (darknet.py:215-229): nn.Linear(prev_filters, out) only works on a (B, Cin) input, i.e. after a
+                    # 1x1 map; its (Cout, Cin) weight has the bytes of a channels-last (Cout, Cin, 1, 1) filter, so it runs as
+                    # a 1x1 convolution with M = B rows
+                    if prev.H != 1 or prev.W != 1:
+                        raise NotImplementedError("connected block %d on a %d x %d map: nn.Linear needs a (B, C) input - put "
+                                                  "an avgpool (or a 1x1 map) in front of it" % (ind, prev.H, prev.W))
+                    k, bn, bnm = 1, False, None
+                    m = net.models[ind]
+                    conv = m[0] if isinstance(m, torch.nn.Sequential) else m
                 cs = _ConvSpec()
                 cs.ind, cs.k = ind, k
-                cs.bn = int(block['batch_normalize']) != 0
+                cs.bn = bn
                 act = block['activation']
                 if act not in ('leaky', 'linear', 'relu'):
                     raise NotImplementedError("activation '%s'" % act)
@@ -284,9 +313,7 @@ class Plan(object):
                     raise NotImplementedError("conv input with a channel count that is not a multiple of 4")
                 cs.H, cs.W = prev.H, prev.W
                 cs.coutp = _pad4(c)
-                seq = net.models[ind]
-                cs.conv = seq[0]
-                cs.bnm = seq[1] if cs.bn else None
+                cs.conv, cs.bnm = conv, bnm
                 # fuse a following 2x2/2 max-pool when it is the only consumer
                 nxt = blocks[ind + 2] if ind + 2 < len(blocks) else None
                 cs.pool = bool(cs.bn and nxt is not None and nxt['type'] == 'maxpool' and int(nxt['size']) == 2 and
@@ -320,11 +347,22 @@ class Plan(object):
                     self.acts[ind] = cs.out
                 self.ops_fwd.append(('conv', cs))
                 prev = cs.out
+                prev_flat = t == 'connected'
+                self.flat[ind] = prev_flat
             elif t == 'maxpool':
                 if ind in self.fused_pool:
                     prev = self.acts[ind]
                     continue
                 k, s = int(block['size']), int(block['stride'])
+                if s == 1:
+                    # MaxPoolStride1 (darknet.py:8-14): 2x2 window over the right / bottom replicate-padded map, H x W out;
+                    # the cfg's size is ignored, as in the reference
+                    src = prev
+                    out = _Act(torch.empty(B * h * w * src.ld, **f32), 0, c, h, w, src.ld)
+                    self.acts[ind] = out
+                    self.ops_fwd.append(('maxpool_s1', ind, src, out))
+                    prev = out
+                    continue
                 if k != 2 or s != 2:
                     raise NotImplementedError("maxpool size=%d stride=%d (MaxPoolStride1, darknet.py:8-14) is not instantiated by the pose cfgs; not built" % (k, s))
                 src = prev
@@ -340,6 +378,38 @@ class Plan(object):
                 self.acts[ind] = out
                 self.ops_fwd.append(('reorg', ind, src, out))
                 prev = out
+            elif t == 'shortcut':
+                f = resolve_layers(block['from'], ind)[0]
+                a, b = self.acts[f], prev
+                if a is None:
+                    raise RuntimeError("shortcut from a layer whose output was fused away")
+                if (a.C, a.H, a.W) != (b.C, b.H, b.W):
+                    raise NotImplementedError("shortcut %d adds layer %d (%d x %d x %d) to layer %d (%d x %d x %d): the "
+                                              "maps must have the same shape" % (ind, f, a.W, a.H, a.C, ind - 1, b.W, b.H, b.C))
+                act = block['activation']
+                if act not in ('leaky', 'linear', 'relu'):
+                    raise NotImplementedError("shortcut activation '%s'" % act)
+                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c))
+                self.acts[ind] = out
+                self.ops_fwd.append(('shortcut', ind, a, b, out, {'leaky': 0.1, 'linear': 1.0, 'relu': 0.0}[act]))
+                prev = out
+                self.flat[ind] = prev_flat
+            elif t == 'avgpool':
+                # GlobalAvgPool2d (darknet.py:37-47): (B, H, W, C) -> (B, C), a 1x1 map downstream
+                src = prev
+                out = _Act(zeros_or_empty(B * _pad4(c), **f32), 0, c, 1, 1, _pad4(c))
+                self.acts[ind] = out
+                self.ops_fwd.append(('avgpool', ind, src, out))
+                prev = out
+                prev_flat = self.flat[ind] = True
+            elif t == 'softmax':
+                # nn.Softmax() (darknet.py:181-184): implicit dim 1 = the channels of each (B, C) row or NHWC pixel
+                src = prev
+                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c))
+                self.acts[ind] = out
+                self.ops_fwd.append(('softmax', ind, src, out))
+                prev = out
+                self.flat[ind] = prev_flat
             elif t == 'route':
                 layers = resolve_layers(block['layers'], ind)
                 srcs = [self.acts[l] for l in layers]
@@ -353,8 +423,10 @@ class Plan(object):
                     self.acts[ind] = out
                     self.ops_fwd.append(('concat', ind, layers, srcs, out))
                 prev = self.acts[ind]
+                prev_flat = self.flat[ind] = self.flat[layers[0]]
             else:  # region / cost: not executed in forward (darknet.py:119-127)
                 self.acts[ind] = prev
+                self.flat[ind] = prev_flat
         # Filter staging buffers are allocated when first needed: channels-last parameters are used in place, so only the
         # padded first layer (or a filter a caller replaced by a plain contiguous tensor) gets a forward / gradient
         # staging copy, and the data-gradient operands (202 MB) exist only in plans that run a backward.
@@ -419,6 +491,7 @@ class Plan(object):
         self.dgrad_ready = None
         self.grads = {}      # layer index -> _Act gradient buffers, allocated on first backward
         self.out_act = self.acts[self.last]
+        self.out_flat = self.flat[self.last]      # forward returns (B, C) instead of (B, C, h, w), as the reference
         self.consumed = False
         self._graph = self._graph_key = self._x_static = self._y_static = None
         self._graph_failed = False
@@ -1221,7 +1294,7 @@ class Plan(object):
             self._hb_gains_after_forward = False
             self._hb_gains = self._bn_gains()
         o = self.out_act
-        y = torch.empty(B, o.C, o.H, o.W, dtype=torch.float32, device=self.device)
+        y = torch.empty(*((B, o.C) if self.out_flat else (B, o.C, o.H, o.W)), dtype=torch.float32, device=self.device)
         call('ssp_nhwc_to_nchw', o.ptr, y.data_ptr(), B, o.C, o.H, o.W, o.ld, st)
         self.consumed = False
         self.was_training = training
@@ -1415,6 +1488,18 @@ class Plan(object):
             elif kind == 'reorg':
                 _, ind, src, out = op
                 call('ssp_reorg', src.ptr, src.ld, out.ptr, out.ld, src.C, B, src.H, src.W, 0, 0, st)
+            elif kind == 'maxpool_s1':
+                _, ind, src, out = op
+                call('ssp_maxpool_s1_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
+            elif kind == 'shortcut':
+                _, ind, a, b, out, slope = op
+                call('ssp_shortcut_fwd', a.ptr, a.ld, b.ptr, b.ld, out.ptr, out.ld, _pad4(out.C), B * out.H * out.W, slope, st)
+            elif kind == 'avgpool':
+                _, ind, src, out = op
+                call('ssp_avgpool_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
+            elif kind == 'softmax':
+                _, ind, src, out = op
+                call('ssp_softmax_fwd', src.ptr, src.ld, out.ptr, out.ld, src.C, B * src.H * src.W, st)
             elif kind == 'concat':
                 _, ind, layers, srcs, out = op
                 off = 0
@@ -1494,7 +1579,8 @@ class Plan(object):
         written.add(src)
 
     def backward(self, grad_out):
-        """grad_out: (B, C, h, w) NCHW.  Returns {param tensor id: grad tensor}."""
+        """grad_out: (B, C, h, w) NCHW, or (B, C) when the network ends in avgpool / connected / softmax.  Returns {param
+        tensor id: grad tensor}."""
         if self.consumed:
             raise RuntimeError("Darknet backward called twice on the same forward: the HIP path rewrites the saved "
                                "conv outputs in place (no retain_graph support)")
@@ -1503,6 +1589,9 @@ class Plan(object):
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
         o = self.out_act
+        if tuple(grad_out.shape) != ((B, o.C) if self.out_flat else (B, o.C, o.H, o.W)):
+            raise ValueError("Darknet backward: gradient of shape %s for an output of shape %s" % (
+                tuple(grad_out.shape), (B, o.C) if self.out_flat else (B, o.C, o.H, o.W)))
         g_last = self._grad_buf(self.last, o)
         call('ssp_nchw_to_nhwc', grad_out.data_ptr(), g_last.ptr, B, o.C, o.H, o.W, o.C, o.ld, st)
         if o.ld > o.C:
@@ -1575,7 +1664,7 @@ class Plan(object):
                 continue
             if t == 'maxpool' and ind in self.fused_pool:
                 continue  # handled by the conv block that owns it
-            if t == 'convolutional':
+            if t in ('convolutional', 'connected'):
                 cs = self.convs[ind]
                 oind = ind + 1 if cs.pool else ind
                 if oind not in written:
@@ -1678,13 +1767,39 @@ class Plan(object):
             elif t == 'maxpool':
                 if ind not in written:
                     continue
-                op = [o_ for o_ in self.ops_fwd if o_[0] == 'maxpool' and o_[1] == ind][0]
+                op = [o_ for o_ in self.ops_fwd if o_[0] in ('maxpool', 'maxpool_s1') and o_[1] == ind][0]
                 _, _, src, out = op
                 sind = producer_of(src)
                 gin = self._grad_buf(sind, src)
                 g = self.grads[ind]
-                call('ssp_maxpool_bwd', src.ptr, src.ld, g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W,
-                     1 if sind in written else 0, st)
+                call('ssp_maxpool_bwd' if op[0] == 'maxpool' else 'ssp_maxpool_s1_bwd', src.ptr, src.ld, g.ptr, g.ld,
+                     gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, 1 if sind in written else 0, st)
+                written.add(sind)
+            elif t == 'shortcut':
+                if ind not in written:
+                    continue
+                _, _, a, b, out, slope = [o_ for o_ in self.ops_fwd if o_[0] == 'shortcut' and o_[1] == ind][0]
+                ia, ib = producer_of(a), producer_of(b)
+                ga, gb = self._grad_buf(ia, a), self._grad_buf(ib, b)
+                g = self.grads[ind]
+                # (from = -1: ia == ib, one buffer - the kernel adds 2 g')
+                call('ssp_shortcut_bwd', g.ptr, g.ld, out.ptr, out.ld, ga.ptr, ga.ld, 1 if ia in written else 0, gb.ptr,
+                     gb.ld, 1 if ib in written else 0, _pad4(out.C), B * out.H * out.W, slope, st)
+                written.add(ia)
+                written.add(ib)
+            elif t in ('avgpool', 'softmax'):
+                if ind not in written:
+                    continue
+                _, _, src, out = [o_ for o_ in self.ops_fwd if o_[0] == t and o_[1] == ind][0]
+                sind = producer_of(src)
+                gin = self._grad_buf(sind, src)
+                g = self.grads[ind]
+                if t == 'avgpool':
+                    call('ssp_avgpool_bwd', g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W,
+                         1 if sind in written else 0, st)
+                else:
+                    call('ssp_softmax_bwd', out.ptr, out.ld, g.ptr, g.ld, gin.ptr, gin.ld, src.C, B * src.H * src.W,
+                         1 if sind in written else 0, st)
                 written.add(sind)
             elif t == 'reorg':
                 if ind not in written:
