@@ -195,24 +195,68 @@ def choose_under_budget(table, budget):
     return choice, moved
 
 
-class _Act(object):
-    """A [pixels][ld] fp32 view: tensor + channel offset."""
-    __slots__ = ('t', 'off', 'C', 'H', 'W', 'ld')
+_SLOPES = {'leaky': 0.1, 'linear': 1.0, 'relu': 0.0}      # negative-side slope of each supported activation
 
-    def __init__(self, t, off, C, H, W, ld):
+
+class _Act(object):
+    """A [pixels][ld] fp32 view: tensor + channel offset.
+
+    producer: the layer whose gradient buffer (Plan.grads) receives this map's gradient - the FIRST layer whose forward
+    output it is (Plan._place): a fused 2x2 pool's output belongs to the pool, a one-layer route (or a region block) passes
+    its source's map on and keeps its producer; None for the network input.  flat: the reference holds this map as a 2-D
+    (B, C) tensor (avgpool, connected, and softmax / shortcut / route of those)."""
+    __slots__ = ('t', 'off', 'C', 'H', 'W', 'ld', 'flat', 'producer')
+
+    def __init__(self, t, off, C, H, W, ld, flat=False):
         self.t, self.off, self.C, self.H, self.W, self.ld = t, off, C, H, W, ld
+        self.flat = flat
+        self.producer = None
 
     @property
     def ptr(self):
         return _ptr(self.t, self.off)
 
 
+class _Op(object):
+    """One executed block other than a conv / connected block (those are _ConvSpec records): its kind ('maxpool',
+    'maxpool_s1', 'reorg', 'shortcut', 'avgpool', 'softmax', 'alias' = one-layer route, 'concat'), layer index, input maps,
+    output map and, for a shortcut, the activation's slope."""
+    __slots__ = ('kind', 'ind', 'srcs', 'out', 'slope')
+
+    def __init__(self, kind, ind, srcs, out, slope=None):
+        self.kind, self.ind, self.srcs, self.out, self.slope = kind, ind, srcs, out, slope
+
+    @property
+    def oind(self):
+        """Layer index holding the output (acts / grads entry)."""
+        return self.ind
+
+
 class _ConvSpec(object):
     """One conv block of a plan.  `raw` (the block's raw conv output, kept for backward) is allocated on first use: the
     fused first block (csrc/conv_first.hip) recomputes its convolution in every pass and never touches it - 1.42 GB at
     batch 64, 416 x 416 that a plan (and the plan cache's memory budget) does not have to carry."""
+    kind = 'conv'
     _raw = None
     _raw_spec = None     # (allocator, floats, tensor kwargs)
+    # set later, by the tuner, the first forward / backward or _plan_bn_fusion
+    wbuf = gbuf = None             # forward-operand / filter-gradient staging of a parameter that is not channels-last
+    wino_u = wino_ud = None        # {tile: Winograd-transformed forward / data-gradient filters}
+    wino_ws = wino_ws_floats = None    # per-layer workspace of a Winograd filter gradient, and its size
+    wgrad_wino = 0                 # filter gradient: 0 = direct, else the Winograd tile (or WGRAD_FUSED)
+    ws_dgrad = 0                   # split-K workspace floats of the data-gradient plan
+    fwd_fams = None                # {family: (code, ms)} the head-error budget chooses from
+    stats = None                   # per-tile BatchNorm partial statistics
+    first_fused = False
+    first_partial = first_wpart = None     # fused first block: BatchNorm / filter-gradient partials
+    bnp = bn_fuse_src = None       # BatchNorm-backward sums folded into the consumer's dgrad (_plan_bn_fusion)
+    v_live = False                 # the forward left the transformed input V in wino_ws for the filter gradient
+    packed = False                 # the parameter is channels-last: used (and its gradient accumulated) in place
+
+    @property
+    def oind(self):
+        """Layer index holding the output (acts / grads entry): the fused pool's, when there is one."""
+        return self.ind + 1 if self.pool else self.ind
 
     @property
     def raw(self):
@@ -270,11 +314,9 @@ class Plan(object):
         self.convs = {}      # layer index -> _ConvSpec
         self.fused_pool = set()   # maxpool layers folded into the preceding conv block
         self.acts = [None] * nl   # forward outputs
-        self.flat = [False] * nl  # layers whose output is 2-D (B, C) in the reference: avgpool, connected, softmax of those
-        self.ops_fwd = []
+        self.ops = []        # one record per executed block (_ConvSpec or _Op), in forward order; backward runs it reversed
         wsz = dsz = 0
         prev = self.input_act
-        prev_flat = False
         for ind, block in enumerate(blocks[1:]):
             t = block['type']
             w, h, c = self.shapes[ind]
@@ -301,9 +343,9 @@ class Plan(object):
                 cs.ind, cs.k = ind, k
                 cs.bn = bn
                 act = block['activation']
-                if act not in ('leaky', 'linear', 'relu'):
+                if act not in _SLOPES:
                     raise NotImplementedError("activation '%s'" % act)
-                cs.slope = {'leaky': 0.1, 'linear': 1.0, 'relu': 0.0}[act]
+                cs.slope = _SLOPES[act]
                 cs.inp = prev
                 cs.first = prev is self.input_act
                 cs.cin = in_c if cs.first else prev.C
@@ -329,6 +371,7 @@ class Plan(object):
                     cs.out = _Act(alloc(B * Ho * Wo * cs.coutp, **f32), 0, c, Ho, Wo, cs.coutp)
                 else:
                     cs.out = _Act(cs.raw, 0, c, cs.H, cs.W, cs.coutp)
+                cs.out.flat = t == 'connected'
                 cs.plan_fwd = cs.plan_dgrad = 0     # explicit igemm plan codes (0 = library heuristic), see _autotune
                 # per-channel vectors: mean, invstd, scale, shift, c1, c2, dgamma, dbeta
                 cs.vec = torch.zeros(8, cs.coutp, **f32)
@@ -341,43 +384,21 @@ class Plan(object):
                 self.convs[ind] = cs
                 if cs.pool:
                     self.fused_pool.add(ind + 1)
-                    self.acts[ind] = None
-                    self.acts[ind + 1] = cs.out
-                else:
-                    self.acts[ind] = cs.out
-                self.ops_fwd.append(('conv', cs))
-                prev = cs.out
-                prev_flat = t == 'connected'
-                self.flat[ind] = prev_flat
+                op = cs
             elif t == 'maxpool':
                 if ind in self.fused_pool:
-                    prev = self.acts[ind]
-                    continue
+                    continue        # prev is the conv block's pooled output
                 k, s = int(block['size']), int(block['stride'])
-                if s == 1:
-                    # MaxPoolStride1 (darknet.py:8-14): 2x2 window over the right / bottom replicate-padded map, H x W out;
-                    # the cfg's size is ignored, as in the reference
-                    src = prev
-                    out = _Act(torch.empty(B * h * w * src.ld, **f32), 0, c, h, w, src.ld)
-                    self.acts[ind] = out
-                    self.ops_fwd.append(('maxpool_s1', ind, src, out))
-                    prev = out
-                    continue
-                if k != 2 or s != 2:
+                # s == 1: MaxPoolStride1 (darknet.py:8-14): 2x2 window over the right / bottom replicate-padded map, H x W
+                # out; the cfg's size is ignored, as in the reference
+                if s != 1 and (k != 2 or s != 2):
                     raise NotImplementedError("maxpool size=%d stride=%d (MaxPoolStride1, darknet.py:8-14) is not instantiated by the pose cfgs; not built" % (k, s))
-                src = prev
-                out = _Act(torch.empty(B * h * w * src.ld, **f32), 0, c, h, w, src.ld)
-                self.acts[ind] = out
-                self.ops_fwd.append(('maxpool', ind, src, out))
-                prev = out
+                op = _Op('maxpool_s1' if s == 1 else 'maxpool', ind, [prev],
+                         _Act(torch.empty(B * h * w * prev.ld, **f32), 0, c, h, w, prev.ld))
             elif t == 'reorg':
                 if int(block['stride']) != 2:
                     raise NotImplementedError("reorg stride != 2")
-                src = prev
-                out = _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c)
-                self.acts[ind] = out
-                self.ops_fwd.append(('reorg', ind, src, out))
-                prev = out
+                op = _Op('reorg', ind, [prev], _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c))
             elif t == 'shortcut':
                 f = resolve_layers(block['from'], ind)[0]
                 a, b = self.acts[f], prev
@@ -387,46 +408,32 @@ class Plan(object):
                     raise NotImplementedError("shortcut %d adds layer %d (%d x %d x %d) to layer %d (%d x %d x %d): the "
                                               "maps must have the same shape" % (ind, f, a.W, a.H, a.C, ind - 1, b.W, b.H, b.C))
                 act = block['activation']
-                if act not in ('leaky', 'linear', 'relu'):
+                if act not in _SLOPES:
                     raise NotImplementedError("shortcut activation '%s'" % act)
-                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c))
-                self.acts[ind] = out
-                self.ops_fwd.append(('shortcut', ind, a, b, out, {'leaky': 0.1, 'linear': 1.0, 'relu': 0.0}[act]))
-                prev = out
-                self.flat[ind] = prev_flat
+                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c), b.flat)
+                op = _Op('shortcut', ind, [a, b], out, _SLOPES[act])
             elif t == 'avgpool':
                 # GlobalAvgPool2d (darknet.py:37-47): (B, H, W, C) -> (B, C), a 1x1 map downstream
-                src = prev
-                out = _Act(zeros_or_empty(B * _pad4(c), **f32), 0, c, 1, 1, _pad4(c))
-                self.acts[ind] = out
-                self.ops_fwd.append(('avgpool', ind, src, out))
-                prev = out
-                prev_flat = self.flat[ind] = True
+                op = _Op('avgpool', ind, [prev], _Act(zeros_or_empty(B * _pad4(c), **f32), 0, c, 1, 1, _pad4(c), True))
             elif t == 'softmax':
                 # nn.Softmax() (darknet.py:181-184): implicit dim 1 = the channels of each (B, C) row or NHWC pixel
-                src = prev
-                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c))
-                self.acts[ind] = out
-                self.ops_fwd.append(('softmax', ind, src, out))
-                prev = out
-                self.flat[ind] = prev_flat
+                out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c), prev.flat)
+                op = _Op('softmax', ind, [prev], out)
             elif t == 'route':
                 layers = resolve_layers(block['layers'], ind)
                 srcs = [self.acts[l] for l in layers]
                 if any(s is None for s in srcs):
                     raise RuntimeError("route to a layer whose output was fused away")
                 if len(layers) == 1:
-                    self.acts[ind] = srcs[0]
-                    self.ops_fwd.append(('alias', ind, layers[0]))
+                    op = _Op('alias', ind, srcs, srcs[0])
                 else:
-                    out = _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c)
-                    self.acts[ind] = out
-                    self.ops_fwd.append(('concat', ind, layers, srcs, out))
-                prev = self.acts[ind]
-                prev_flat = self.flat[ind] = self.flat[layers[0]]
+                    op = _Op('concat', ind, srcs, _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c, srcs[0].flat))
             else:  # region / cost: not executed in forward (darknet.py:119-127)
-                self.acts[ind] = prev
-                self.flat[ind] = prev_flat
+                self._place(ind, prev)
+                continue
+            self.ops.append(op)
+            self._place(op.oind, op.out)
+            prev = op.out
         # Filter staging buffers are allocated when first needed: channels-last parameters are used in place, so only the
         # padded first layer (or a filter a caller replaced by a plain contiguous tensor) gets a forward / gradient
         # staging copy, and the data-gradient operands (202 MB) exist only in plans that run a backward.
@@ -491,10 +498,16 @@ class Plan(object):
         self.dgrad_ready = None
         self.grads = {}      # layer index -> _Act gradient buffers, allocated on first backward
         self.out_act = self.acts[self.last]
-        self.out_flat = self.flat[self.last]      # forward returns (B, C) instead of (B, C, h, w), as the reference
+        self.out_flat = self.out_act.flat      # forward returns (B, C) instead of (B, C, h, w), as the reference
         self.consumed = False
         self._graph = self._graph_key = self._x_static = self._y_static = None
         self._graph_failed = False
+
+    def _place(self, ind, act):
+        """acts[ind] = act; the first layer to hold a map is its producer (see _Act)."""
+        self.acts[ind] = act
+        if act.producer is None:
+            act.producer = ind
 
     def _size_layer(self, cs):
         """Statistics / split-K bookkeeping of one conv block for its CURRENT forward plan code (after tuning, and again
@@ -506,11 +519,11 @@ class Plan(object):
         cs.tile_m = q('ssp_conv_stats_tile_m', cs.plan_fwd)
         cs.ws_fwd = q('ssp_conv_workspace_floats', cs.plan_fwd)
         cs.ntile = q('ssp_conv_stats_tiles', cs.plan_fwd)
-        codes = set([cs.plan_fwd, 0] + [c for c, _ in (getattr(cs, 'fwd_fams', None) or {}).values()])
+        codes = set([cs.plan_fwd, 0] + [c for c, _ in (cs.fwd_fams or {}).values()])
         nstat = max(q('ssp_conv_stats_floats', c) for c in codes)
-        if getattr(cs, 'first_fused', False):
+        if cs.first_fused:
             nstat = max(nstat, cs.first_groups * 64)
-        if cs.bn and (getattr(cs, 'stats', None) is None or cs.stats.numel() < nstat):
+        if cs.bn and (cs.stats is None or cs.stats.numel() < nstat):
             cs.stats = torch.empty(nstat, dtype=torch.float32, device=self.device)
 
     def _apply_head_budget(self):
@@ -540,7 +553,7 @@ class Plan(object):
         budget = float(os.environ.get('SSP_HEAD_ERR_BUDGET', '3.5e-5'))
         if budget <= 0 or not self._tune:
             return
-        cand = [cs for cs in self.convs.values() if wino_tile(cs.plan_fwd) and 0 in (getattr(cs, 'fwd_fams', None) or {})]
+        cand = [cs for cs in self.convs.values() if wino_tile(cs.plan_fwd) and 0 in (cs.fwd_fams or {})]
         if not cand:
             return
         # the NETWORK is part of the key: the deviations are properties of this stack of layers (another cfg at the same input
@@ -611,7 +624,7 @@ class Plan(object):
         for cs in cand:
             cs.plan_fwd = rec['chosen'].get(cs.ind, cs.plan_fwd)
             self._size_layer(cs)
-            cs.wino_u = {t: b for t, b in (getattr(cs, 'wino_u', None) or {}).items() if t == wino_tile(cs.plan_fwd)}
+            cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
         self._fit_workspace()
         self.head_budget = rec
         # the amplification the decisions were measured under (head_budget_drifted).  A record adopted from the cache ran no
@@ -636,7 +649,7 @@ class Plan(object):
                 _HEAD_BUDGET_PINNED.pop(k, None)
             # every timed family is a candidate again
             for cs in self.convs.values():
-                fams = getattr(cs, 'fwd_fams', None)
+                fams = cs.fwd_fams
                 if fams:
                     best = min((v for v in fams.values() if v[1] is not None), key=lambda v: v[1], default=None)
                     if best is not None and best[0] != cs.plan_fwd:
@@ -669,7 +682,7 @@ class Plan(object):
         if stage == 0:
             mine = [self.convs[i].plan_fwd for i in order]
         else:
-            mine = [self.convs[i].plan_dgrad for i in order] + [getattr(self.convs[i], 'wgrad_wino', 0) for i in order]
+            mine = [self.convs[i].plan_dgrad for i in order] + [self.convs[i].wgrad_wino for i in order]
         head = [self.B, self.H, self.W, stage, len(order)]
         got = fn(head + mine)
         # Adopt only when EVERY rank can: same plan shape everywhere, and every code one this rank's environment allows
@@ -700,7 +713,7 @@ class Plan(object):
             else:
                 cs.plan_dgrad = vals[k]
                 w = vals[len(order) + k]
-                if w != getattr(cs, 'wgrad_wino', 0):
+                if w != cs.wgrad_wino:
                     cs.wgrad_wino = w
                     if w:
                         cs.wino_ws_floats = _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', self.B, cs.H, cs.W, cs.cinp, cs.cout, w)
@@ -709,57 +722,54 @@ class Plan(object):
             self._fit_workspace()
 
     def _fit_workspace(self):
-        need = max([1] + [cs.ws_fwd for cs in self.convs.values()] + [getattr(cs, 'ws_dgrad', 0) for cs in self.convs.values()])
+        need = max([1] + [cs.ws_fwd for cs in self.convs.values()] + [cs.ws_dgrad for cs in self.convs.values()])
         if need > self.ws_floats:
             torch.cuda.current_stream().synchronize()      # nothing in flight may still use the old workspace
             self.ws_floats = need
             self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
             self._graph = None          # a captured inference chain holds the old workspace pointer
 
-    def footprint(self):
-        """Bytes of device memory this plan's forward buffers hold or will hold after a training-mode forward (each storage
-        counted once; raw conv outputs are allocated on first use - every block's but the fused first one's count here)."""
-        seen, total = set(), 0
+    def _forward_tensors(self):
         ts = [self.x_nhwc, self.ws, self.bn_partial] + [a.t for a in self.acts if a is not None]
         for cs in self.convs.values():
-            ts += [cs._raw, cs.vec, getattr(cs, 'stats', None), getattr(cs, 'first_partial', None)]
-            if cs._raw is None and not getattr(cs, 'first_fused', False):
-                total += cs._raw_spec[1] * 4
+            ts += [cs._raw, cs.vec, cs.stats, cs.first_partial]
+        return ts
+
+    @staticmethod
+    def _distinct_bytes(ts):
+        """Bytes of the distinct storages among tensors ts (None entries skipped)."""
+        seen, total = set(), 0
         for t in ts:
             if t is not None and t.data_ptr() not in seen:
                 seen.add(t.data_ptr())
                 total += t.numel() * t.element_size()
         return total
+
+    def footprint(self):
+        """Bytes of device memory this plan's forward buffers hold or will hold after a training-mode forward (each storage
+        counted once; raw conv outputs are allocated on first use - every block's but the fused first one's count here)."""
+        pending = sum(cs._raw_spec[1] * 4 for cs in self.convs.values() if cs._raw is None and not cs.first_fused)
+        return pending + self._distinct_bytes(self._forward_tensors())
 
     def nbytes_now(self):
         """Bytes of device memory the plan holds right now: forward buffers, and whatever the first backward and the tuner
         added since (gradient buffers, data-gradient operands, Winograd filters and per-layer workspaces)."""
-        seen, total = set(), 0
-        ts = [self.x_nhwc, self.ws, self.bn_partial, self._dpack] + [a.t for a in self.acts if a is not None]
-        ts += [g.t for g in self.grads.values()]
+        ts = self._forward_tensors() + [self._dpack] + [g.t for g in self.grads.values()]
         for cs in self.convs.values():
-            ts += [cs._raw, cs.vec, getattr(cs, 'stats', None), getattr(cs, 'first_partial', None), getattr(cs, 'wbuf', None),
-                   getattr(cs, 'gbuf', None), getattr(cs, 'wino_ws', None), getattr(cs, 'first_wpart', None)]
-            ts += list((getattr(cs, 'wino_u', None) or {}).values()) + list((getattr(cs, 'wino_ud', None) or {}).values())
-            bnp = getattr(cs, 'bnp', None)
-            if bnp is not None:
-                ts.append(bnp[0])
-        for t in ts:
-            if t is not None and t.data_ptr() not in seen:
-                seen.add(t.data_ptr())
-                total += t.numel() * t.element_size()
-        return total
+            ts += [cs.wbuf, cs.gbuf, cs.wino_ws, cs.first_wpart, cs.bnp[0] if cs.bnp is not None else None]
+            ts += list((cs.wino_u or {}).values()) + list((cs.wino_ud or {}).values())
+        return self._distinct_bytes(ts)
 
     # ------------------------------------------------------------------ lazily allocated filter staging
     def _wbuf(self, cs):
-        if getattr(cs, 'wbuf', None) is None:
+        if cs.wbuf is None:
             cs.wbuf = torch.empty(cs.cout * cs.k * cs.k * cs.cinp, dtype=torch.float32, device=self.device)
         return cs.wbuf
 
     def _wino_u(self, cs, tile):
         """Winograd-transformed forward filters [(tile+2)^2][Cout][Cin] of a layer whose forward plan is a Winograd code of
         that tile size (one buffer per tile size; the tuner drops the ones it did not choose)."""
-        if getattr(cs, 'wino_u', None) is None:
+        if cs.wino_u is None:
             cs.wino_u = {}
         if tile not in cs.wino_u:
             cs.wino_u[tile] = torch.empty((tile + 2) ** 2 * cs.cout * cs.cinp, dtype=torch.float32, device=self.device)
@@ -767,7 +777,7 @@ class Plan(object):
 
     def _wino_ud(self, cs, tile):
         """... and of the data-gradient operand [(tile+2)^2][Cin][Cout] (from the flipped / transposed [Cin][tap][Cout] layout)."""
-        if getattr(cs, 'wino_ud', None) is None:
+        if cs.wino_ud is None:
             cs.wino_ud = {}
         if tile not in cs.wino_ud:
             cs.wino_ud[tile] = torch.empty((tile + 2) ** 2 * cs.cin * cs.coutp, dtype=torch.float32, device=self.device)
@@ -778,7 +788,7 @@ class Plan(object):
         side stream).  When the layer's forward plan is a Winograd code too, the training forward is handed this same
         buffer (V | M): the transformed input V it leaves at the head is what the filter gradient needs, so the layer
         input is transformed once per step (csrc/conv_wgrad.hip ssp_conv_wgrad_wino_launch, x == NULL)."""
-        if getattr(cs, 'wino_ws', None) is None:
+        if cs.wino_ws is None:
             n = cs.wino_ws_floats
             if wino_tile(cs.plan_fwd) and not wino_fused(cs.plan_fwd):
                 n = max(n, _lib.query('ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, cs.plan_fwd))
@@ -786,7 +796,7 @@ class Plan(object):
         return cs.wino_ws
 
     def _gbuf(self, cs):
-        if getattr(cs, 'gbuf', None) is None:
+        if cs.gbuf is None:
             cs.gbuf = torch.empty(cs.cout * cs.k * cs.k * cs.cinp, dtype=torch.float32, device=self.device)
         return cs.gbuf
 
@@ -819,17 +829,11 @@ class Plan(object):
                 cs.wgrad_wino = 0
         if tune:
             self._sync_codes(1)              # multi-GPU: ... and rank 0's data- / filter-gradient choices
-        need = 1
         for cs in self.convs.values():
             cs.ws_dgrad = 0 if cs.first else _lib.query('ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp,
                                                         cs.cin, cs.k, cs.plan_dgrad)
-            need = max(need, cs.ws_dgrad)
         self._plan_bn_fusion()
-        if need > self.ws_floats:
-            torch.cuda.current_stream().synchronize()      # nothing in flight may still use the old workspace
-            self.ws_floats = need
-            self.ws = torch.empty(need, dtype=torch.float32, device=self.device)
-            self._graph = None          # a captured inference chain holds the old workspace pointer
+        self._fit_workspace()
 
     def _wgrad_key(self, cs):
         return ('wgrad', self.B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw, cs.inp.ld, _tune_tag())
@@ -970,11 +974,7 @@ class Plan(object):
         for cs in self.convs.values():
             if cs.first:
                 continue
-            src = None
-            for i, a in enumerate(self.acts):
-                if a is cs.inp:
-                    src = i
-                    break
+            src = cs.inp.producer
             scs = self.convs.get(src)
             if (scs is None or scs.pool or not scs.bn or not scs.needs_act or scs.out is not cs.inp or
                     self.consumers[src] != [cs.ind] or scs.coutp != scs.cout or cs.cin != scs.cout or
@@ -1232,7 +1232,7 @@ class Plan(object):
                 if 0 not in cs.fwd_fams and 0 in fams_:
                     cs.fwd_fams[0] = (0, fams_[0][1])
                 # not chosen: the transformed-filter buffers go back to the allocator
-                cs.wino_u = {t: b for t, b in (getattr(cs, 'wino_u', None) or {}).items() if t == wino_tile(cs.plan_fwd)}
+                cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
             if which == 'dgrad' and not cs.first and cs.coutp % 16 == 0 and (cs.cin > 64 or wino_codes(cs, which)):
                 key = self._dgrad_key(cs)
                 wslice = self._dpack[cs.doff:cs.doff + cs.cinp * cs.k * cs.k * cs.coutp]
@@ -1255,7 +1255,7 @@ class Plan(object):
                 cs.plan_dgrad = admitted(code, key, launch, lambda cs=cs: gscratch[:cs.M * cs.inp.ld],
                                          [(cs.raw, cs.ldraw, 0, cs.cout), wslice], None,
                                          (lambda code=code: prep_d(wino_tile(code))) if wino_tile(code) else None)
-                cs.wino_ud = {t: b for t, b in (getattr(cs, 'wino_ud', None) or {}).items() if t == wino_tile(cs.plan_dgrad)}
+                cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
         torch.cuda.synchronize()
         if len(_TUNE_CACHE) != n_known:
             _tune_cache_save()
@@ -1314,21 +1314,19 @@ class Plan(object):
         # epoch, load_weights invalidates explicitly); training: weights change every step, always repack.
         # Parameters stored channels-last (Darknet builds them that way) ARE the forward operand: nothing to repack.
         stale = []
-        for op in self.ops_fwd:
-            if op[0] == 'conv':
-                cs = op[1]
-                wt = cs.conv.weight
-                cs.packed = _is_packed(wt, cs.cinp)
-                if cs.packed:
-                    continue
-                key = (wt.data_ptr(), wt._version, _WEIGHTS_EPOCH[0])
-                if inline_repack:
-                    # graph capture: the repack is part of the captured chain (stays on this stream, runs every replay)
-                    call('ssp_repack_fwd', wt.detach().contiguous().data_ptr(), self._wbuf(cs).data_ptr(), cs.cout,
-                         cs.cin, cs.cinp, cs.k, st)
-                    self.wversion.pop(cs.ind, None)
-                elif training or self.wversion.get(cs.ind) != key:
-                    stale.append((cs, key))
+        for cs in self.convs.values():
+            wt = cs.conv.weight
+            cs.packed = _is_packed(wt, cs.cinp)
+            if cs.packed:
+                continue
+            key = (wt.data_ptr(), wt._version, _WEIGHTS_EPOCH[0])
+            if inline_repack:
+                # graph capture: the repack is part of the captured chain (stays on this stream, runs every replay)
+                call('ssp_repack_fwd', wt.detach().contiguous().data_ptr(), self._wbuf(cs).data_ptr(), cs.cout,
+                     cs.cin, cs.cinp, cs.k, st)
+                self.wversion.pop(cs.ind, None)
+            elif training or self.wversion.get(cs.ind) != key:
+                stale.append((cs, key))
         if need_grad:
             self._prepare_backward()
         # Winograd-plan layers read TRANSFORMED filters: re-derived when the weights may have changed (every training
@@ -1398,114 +1396,118 @@ class Plan(object):
         waited = set()
         if training:
             self.net._bn_epoch += 1       # running statistics change below: every plan's inference constants are stale
-        for op in self.ops_fwd:
-            kind = op[0]
+        for op in self.ops:
+            kind = op.kind
             if kind == 'conv':
-                cs = op[1]
-                ev = wait_for.get(cs.ind)
-                if ev is not None and id(ev) not in waited:
-                    torch.cuda.current_stream().wait_event(ev)      # this layer's packed filters are ready
-                    waited.add(id(ev))
-                bias = cs.conv.bias.data_ptr() if cs.conv.bias is not None else None
-                use_stats = cs.bn and training
-                v = cs.vec
-                if cs.bn and not training:
-                    # inference-mode BatchNorm is a per-channel affine map of constants: recomputed only when one of
-                    # its four tensors changed (in-place updates bump _version; load_weights / fused SGD bump the epoch)
-                    bn = cs.bnm
-                    # (a training-mode forward rewrites running_mean / running_var through raw pointers and reuses the
-                    # scale / shift vectors for the batch statistics: it bumps the net's BN epoch, also part of the key)
-                    bkey = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean,
-                                                                     bn.running_var)) + (_WEIGHTS_EPOCH[0],
-                                                                                         self.net._bn_epoch)
-                    if inline_repack or self.bnversion.get(cs.ind) != bkey:
-                        call('ssp_bn_eval_prepare', cs.cout, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                             bn.running_mean.data_ptr(), bn.running_var.data_ptr(), BN_EPS, v[0].data_ptr(),
-                             v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), st)
-                        self.bnversion[cs.ind] = None if inline_repack else bkey
-                wptr = cs.conv.weight.data_ptr() if cs.packed else self._wbuf(cs).data_ptr()
-                if wino_tile(cs.plan_fwd):
-                    wptr = self._wino_u(cs, wino_tile(cs.plan_fwd)).data_ptr()
-                cs.first_live = False
-                if cs.first_fused and not cs.packed and (training or not need_grad):
-                    # training: statistics pass + apply pass; inference: the apply pass alone with the running-statistics
-                    # affine (v[2], v[3] from ssp_bn_eval_prepare above) - conv + BN + leaky + pool in one launch, the
-                    # full-resolution map is never written (672 x 672, batch 1: 12 us instead of 23 + 12)
-                    if training:
-                        bn = cs.bnm
-                        call('ssp_first_fwd_stats', cs.inp.ptr, wptr, cs.stats.data_ptr(), B, cs.H, cs.W, st)
-                        call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.first_groups, cs.first_tile, cs.M, cs.cout,
-                             bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                             bn.running_var.data_ptr(), self.bn_momentum, BN_EPS, v[0].data_ptr(), v[1].data_ptr(),
-                             v[2].data_ptr(), v[3].data_ptr(), st)
-                    call('ssp_first_fwd_apply', cs.inp.ptr, wptr, v[2].data_ptr(), v[3].data_ptr(), cs.slope,
-                         cs.out.ptr, cs.out.ld, B, cs.H, cs.W, st)
-                    cs.first_live = training        # only a training-mode forward can be followed by the fused backward
-                    continue
-                if not training and not need_grad and cs.needs_act and not cs.pool and cs.coutp == cs.cout:
-                    # inference, un-pooled block: BatchNorm affine + leaky folded into the conv epilogue - one launch,
-                    # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps)
-                    call('ssp_conv_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
-                         v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld,
-                         cs.out.ld, cs.k, cs.plan_fwd, self.ws.data_ptr(), self.ws_floats, st)
-                    continue
-                ws_t = self.ws
-                cs.v_live = False
-                share_v = os.environ.get('SSP_WINO_SHARE_V', '1') != '0'
-                if (need_grad and wino_tile(cs.plan_fwd) and not wino_fused(cs.plan_fwd) and
-                        getattr(cs, 'wgrad_wino', 0) == wino_tile(cs.plan_fwd) and share_v):
-                    ws_t = self._wino_ws(cs)         # V stays at the head of this buffer for the layer's filter gradient
-                    cs.v_live = True
-                elif (need_grad and getattr(cs, 'wgrad_wino', 0) and share_v and self.side_stream is not None and
-                        os.environ.get('SSP_WINO_EARLY_V', '0') == '1'):
-                    # The filter gradient runs in the Winograd domain but this forward launch does not leave its V behind (the
-                    # error budget moved the layer to a direct code, or to the other tile size): the input transform the
-                    # filter gradient needs CAN be queued now on the second stream (SSP_WINO_EARLY_V=1) - an HBM-bound pass next
-                    # to the forward launches instead of inside the backward pass.  Measured on one box, two interleaved rounds
-                    # (profiles/r05_step_ab.txt): 27.48 / 27.57 ms with it, 27.38 / 27.47 without - the transform slows the
-                    # MFMA-bound direct launches it runs beside by as much as it saves later; off by default.
-                    wws = self._wino_ws(cs)
-                    ready = torch.cuda.current_stream().record_event()      # the layer's input is complete on the main stream
-                    self.side_stream.wait_event(ready)
-                    call('ssp_wino_input_transform_t', cs.inp.ptr, cs.inp.ld, wws.data_ptr(), B, cs.H, cs.W, cs.cinp,
-                         cs.wgrad_wino, self.side_stream.cuda_stream)
-                    cs.v_live = True
-                call('ssp_conv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias,
-                     cs.stats.data_ptr() if use_stats else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
-                     cs.k, 0, cs.plan_fwd, ws_t.data_ptr(), ws_t.numel(), st)
-                if cs.bn and training:
-                    bn = cs.bnm
-                    call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.ntile, cs.tile_m, cs.M, cs.cout,
-                         bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                         bn.running_var.data_ptr(), self.bn_momentum, BN_EPS, v[0].data_ptr(), v[1].data_ptr(),
-                         v[2].data_ptr(), v[3].data_ptr(), st)
-                if cs.needs_act:
-                    call('ssp_bn_act_fwd', cs.raw.data_ptr(), cs.ldraw, cs.out.ptr, cs.out.ld, v[2].data_ptr(),
-                         v[3].data_ptr(), cs.coutp, B, cs.H, cs.W, 1 if cs.pool else 0, cs.slope, st)
-            elif kind == 'maxpool':
-                _, ind, src, out = op
+                self._conv_fwd(op, training, need_grad, inline_repack, wait_for, waited, st)
+                continue
+            out = op.out
+            src = op.srcs[0]
+            if kind == 'maxpool':
                 call('ssp_maxpool_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
-            elif kind == 'reorg':
-                _, ind, src, out = op
-                call('ssp_reorg', src.ptr, src.ld, out.ptr, out.ld, src.C, B, src.H, src.W, 0, 0, st)
             elif kind == 'maxpool_s1':
-                _, ind, src, out = op
                 call('ssp_maxpool_s1_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
+            elif kind == 'reorg':
+                call('ssp_reorg', src.ptr, src.ld, out.ptr, out.ld, src.C, B, src.H, src.W, 0, 0, st)
             elif kind == 'shortcut':
-                _, ind, a, b, out, slope = op
-                call('ssp_shortcut_fwd', a.ptr, a.ld, b.ptr, b.ld, out.ptr, out.ld, _pad4(out.C), B * out.H * out.W, slope, st)
+                a, b = op.srcs
+                call('ssp_shortcut_fwd', a.ptr, a.ld, b.ptr, b.ld, out.ptr, out.ld, _pad4(out.C), B * out.H * out.W, op.slope,
+                     st)
             elif kind == 'avgpool':
-                _, ind, src, out = op
                 call('ssp_avgpool_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
             elif kind == 'softmax':
-                _, ind, src, out = op
                 call('ssp_softmax_fwd', src.ptr, src.ld, out.ptr, out.ld, src.C, B * src.H * src.W, st)
             elif kind == 'concat':
-                _, ind, layers, srcs, out = op
                 off = 0
-                for s in srcs:
+                for s in op.srcs:
                     call('ssp_copy_channels', s.ptr, s.ld, _ptr(out.t, off), out.ld, s.C, B * s.H * s.W, 0, st)
                     off += s.C
+            # ('alias', a one-layer route: its output is the source's map, nothing to run)
+
+    def _conv_fwd(self, cs, training, need_grad, inline_repack, wait_for, waited, st):
+        """Forward launches of conv block `cs` (waiting first for its filters from the side stream, see _forward_body)."""
+        B = self.B
+        call = _lib.call
+        ev = wait_for.get(cs.ind)
+        if ev is not None and id(ev) not in waited:
+            torch.cuda.current_stream().wait_event(ev)      # this layer's packed filters are ready
+            waited.add(id(ev))
+        bias = cs.conv.bias.data_ptr() if cs.conv.bias is not None else None
+        use_stats = cs.bn and training
+        v = cs.vec
+        if cs.bn and not training:
+            # inference-mode BatchNorm is a per-channel affine map of constants: recomputed only when one of
+            # its four tensors changed (in-place updates bump _version; load_weights / fused SGD bump the epoch)
+            bn = cs.bnm
+            # (a training-mode forward rewrites running_mean / running_var through raw pointers and reuses the
+            # scale / shift vectors for the batch statistics: it bumps the net's BN epoch, also part of the key)
+            bkey = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean,
+                                                             bn.running_var)) + (_WEIGHTS_EPOCH[0],
+                                                                                 self.net._bn_epoch)
+            if inline_repack or self.bnversion.get(cs.ind) != bkey:
+                call('ssp_bn_eval_prepare', cs.cout, bn.weight.data_ptr(), bn.bias.data_ptr(),
+                     bn.running_mean.data_ptr(), bn.running_var.data_ptr(), BN_EPS, v[0].data_ptr(),
+                     v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), st)
+                self.bnversion[cs.ind] = None if inline_repack else bkey
+        wptr = cs.conv.weight.data_ptr() if cs.packed else self._wbuf(cs).data_ptr()
+        if wino_tile(cs.plan_fwd):
+            wptr = self._wino_u(cs, wino_tile(cs.plan_fwd)).data_ptr()
+        cs.first_live = False
+        if cs.first_fused and not cs.packed and (training or not need_grad):
+            # training: statistics pass + apply pass; inference: the apply pass alone with the running-statistics
+            # affine (v[2], v[3] from ssp_bn_eval_prepare above) - conv + BN + leaky + pool in one launch, the
+            # full-resolution map is never written (672 x 672, batch 1: 12 us instead of 23 + 12)
+            if training:
+                bn = cs.bnm
+                call('ssp_first_fwd_stats', cs.inp.ptr, wptr, cs.stats.data_ptr(), B, cs.H, cs.W, st)
+                call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.first_groups, cs.first_tile, cs.M, cs.cout,
+                     bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                     bn.running_var.data_ptr(), self.bn_momentum, BN_EPS, v[0].data_ptr(), v[1].data_ptr(),
+                     v[2].data_ptr(), v[3].data_ptr(), st)
+            call('ssp_first_fwd_apply', cs.inp.ptr, wptr, v[2].data_ptr(), v[3].data_ptr(), cs.slope,
+                 cs.out.ptr, cs.out.ld, B, cs.H, cs.W, st)
+            cs.first_live = training        # only a training-mode forward can be followed by the fused backward
+            return
+        if not training and not need_grad and cs.needs_act and not cs.pool and cs.coutp == cs.cout:
+            # inference, un-pooled block: BatchNorm affine + leaky folded into the conv epilogue - one launch,
+            # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps)
+            call('ssp_conv_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
+                 v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld,
+                 cs.out.ld, cs.k, cs.plan_fwd, self.ws.data_ptr(), self.ws_floats, st)
+            return
+        ws_t = self.ws
+        cs.v_live = False
+        share_v = os.environ.get('SSP_WINO_SHARE_V', '1') != '0'
+        if (need_grad and wino_tile(cs.plan_fwd) and not wino_fused(cs.plan_fwd) and
+                cs.wgrad_wino == wino_tile(cs.plan_fwd) and share_v):
+            ws_t = self._wino_ws(cs)         # V stays at the head of this buffer for the layer's filter gradient
+            cs.v_live = True
+        elif (need_grad and cs.wgrad_wino and share_v and self.side_stream is not None and
+                os.environ.get('SSP_WINO_EARLY_V', '0') == '1'):
+            # The filter gradient runs in the Winograd domain but this forward launch does not leave its V behind (the
+            # error budget moved the layer to a direct code, or to the other tile size): the input transform the
+            # filter gradient needs CAN be queued now on the second stream (SSP_WINO_EARLY_V=1) - an HBM-bound pass next
+            # to the forward launches instead of inside the backward pass.  Measured on one box, two interleaved rounds
+            # (profiles/r05_step_ab.txt): 27.48 / 27.57 ms with it, 27.38 / 27.47 without - the transform slows the
+            # MFMA-bound direct launches it runs beside by as much as it saves later; off by default.
+            wws = self._wino_ws(cs)
+            ready = torch.cuda.current_stream().record_event()      # the layer's input is complete on the main stream
+            self.side_stream.wait_event(ready)
+            call('ssp_wino_input_transform_t', cs.inp.ptr, cs.inp.ld, wws.data_ptr(), B, cs.H, cs.W, cs.cinp,
+                 cs.wgrad_wino, self.side_stream.cuda_stream)
+            cs.v_live = True
+        call('ssp_conv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias,
+             cs.stats.data_ptr() if use_stats else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
+             cs.k, 0, cs.plan_fwd, ws_t.data_ptr(), ws_t.numel(), st)
+        if cs.bn and training:
+            bn = cs.bnm
+            call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.ntile, cs.tile_m, cs.M, cs.cout,
+                 bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                 bn.running_var.data_ptr(), self.bn_momentum, BN_EPS, v[0].data_ptr(), v[1].data_ptr(),
+                 v[2].data_ptr(), v[3].data_ptr(), st)
+        if cs.needs_act:
+            call('ssp_bn_act_fwd', cs.raw.data_ptr(), cs.ldraw, cs.out.ptr, cs.out.ld, v[2].data_ptr(),
+                 v[3].data_ptr(), cs.coutp, B, cs.H, cs.W, 1 if cs.pool else 0, cs.slope, st)
 
     # ------------------------------------------------------------------ inference as one hipGraph
     def _graph_tensors(self):
@@ -1562,7 +1564,7 @@ class Plan(object):
         call = _lib.call
         B = self.B
         gin = self._grad_buf(src, cs.inp)
-        scs = getattr(cs, 'bn_fuse_src', None)
+        scs = cs.bn_fuse_src
         dwt = (self._wino_ud(cs, wino_tile(cs.plan_dgrad)).data_ptr() if wino_tile(cs.plan_dgrad)
                else _ptr(self._dpack, cs.doff))
         if scs is not None and src not in written:
@@ -1618,7 +1620,6 @@ class Plan(object):
         B = self.B
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
-        blocks = self.net.blocks
         written = set()
         fused_stats = set()      # blocks whose BatchNorm-backward reductions were produced by their consumer's dgrad launch
         written.add(self.last)
@@ -1630,7 +1631,6 @@ class Plan(object):
         # overlaps the dgrad(l) -> BN-backward(l-1) chain of the main stream and fills the idle CUs of its last wave.
         main = torch.cuda.current_stream()
         side = main if self.serial_backward else self.side_stream
-        st2 = side.cuda_stream
         if self.dgrad_ready is not None:
             main.wait_event(self.dgrad_ready)       # dgrad filter repacks were queued during forward
         else:
@@ -1640,7 +1640,6 @@ class Plan(object):
                 if not cs.first:
                     self._repack_dgrad(cs, main)
         out_grads = {}
-        training = self.was_training
         tail_sched = side is not main and os.environ.get('SSP_TAIL_SCHED', '1') != '0'
         if self.reducer is not None:
             self.reducer.begin(flat)
@@ -1651,184 +1650,150 @@ class Plan(object):
                 return torch.as_strided(flat, shape, prm.stride(), off)
             return flat[off:off + n].view(shape)
 
-        def producer_of(act):
-            for i, a in enumerate(self.acts):
-                if a is act:
-                    return i
-            return None
+        def grad_in(a):
+            """Gradient buffer of map a's producer, and whether the launch accumulates into it (marks it written)."""
+            gin = self._grad_buf(a.producer, a)
+            acc = 1 if a.producer in written else 0
+            written.add(a.producer)
+            return gin, acc
 
-        for ind in range(self.nl - 1, -1, -1):
-            block = blocks[ind + 1]
-            t = block['type']
-            if t in ('region', 'cost'):
-                continue
-            if t == 'maxpool' and ind in self.fused_pool:
-                continue  # handled by the conv block that owns it
-            if t in ('convolutional', 'connected'):
-                cs = self.convs[ind]
-                oind = ind + 1 if cs.pool else ind
-                if oind not in written:
-                    continue
-                g = self.grads[oind]
-                v = cs.vec
-                if cs.first_live:
-                    # first block, fused form: both backward passes recompute the convolution from the input
-                    dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
-                    out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
-                    wptr = self._wbuf(cs).data_ptr()
-                    call('ssp_first_bwd_reduce', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
-                         v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
-                    call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
-                         1 if training else 0, 0, dgam.data_ptr(), dbet.data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
-                    # The step's tail is a dependency chain: dgrad of the block's consumer -> this reduce -> this filter
-                    # gradient (HBM-bound: it re-reads the 1.4 GB output gradient).  With the tail schedule the consumer's
-                    # filter gradient (MFMA-bound) was held back behind its data gradient and is running on the side
-                    # stream NOW: this pass stays on the main stream and overlaps it, instead of queueing behind it.
-                    fst = st if tail_sched else st2
-                    if not tail_sched:
-                        side.wait_stream(main)
-                    gw = gview(cs.conv.weight, False)
-                    if getattr(cs, 'first_wpart', None) is None:      # per-workgroup partial gradients, summed in float64
-                        cs.first_wpart = torch.empty(_lib.query('ssp_first_wgrad_workspace_floats', B, cs.H, cs.W),
-                                                     dtype=torch.float32, device=self.device)
-                    call('ssp_first_bwd_wgrad', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
-                         v[0].data_ptr(), v[1].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), cs.slope,
-                         self._gbuf(cs).data_ptr(), cs.first_wpart.data_ptr(), cs.first_wpart.numel(), B, cs.H, cs.W, fst)
-                    call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, fst)
-                    out_grads[id(cs.conv.weight)] = gw
-                    if self.reducer is not None:
-                        if tail_sched:
-                            side.wait_stream(main)
-                        with torch.cuda.stream(side):
-                            self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
-                    continue
-                if cs.needs_act:
-                    if cs.bn and cs.coutp == cs.cout:
-                        dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
-                        out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
-                        dg_ptr, db_ptr = dgam.data_ptr(), dbet.data_ptr()
-                        # two-level reduction (per-workgroup partials -> fp64 finalize).  The single-pass form of
-                        # ssp_bn_act_bwd (atomics into the zeroed gradient, no finalize launch) measured 1.1 ms SLOWER
-                        # per step: 1024 workgroups hammering the same 2*C addresses serialise in the L2.
-                        partial = self.bn_partial.data_ptr()
-                    else:
-                        dg_ptr, db_ptr = v[6].data_ptr(), v[7].data_ptr()
-                        partial = self.bn_partial.data_ptr()
-                    if cs.ind in fused_stats:
-                        # the two reductions came out of the consumer's data-gradient launch: finalize + apply only
-                        ptile, rows, folded = cs.bnp
-                        call('ssp_bn_act_bwd_partials', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(),
-                             cs.ldraw, v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B,
-                             cs.H, cs.W, cs.slope, 1 if training else 0, ptile.data_ptr(), rows, 1 if folded else 0,
-                             dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
-                    else:
-                        call('ssp_bn_act_bwd', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(), cs.ldraw,
-                             v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B, cs.H, cs.W,
-                             1 if cs.pool else 0, cs.slope, 1 if (training and cs.bn) else 0, partial,
-                             dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
-                    dy_ptr, dy_ld = cs.raw.data_ptr(), cs.ldraw
-                    if cs.bn and cs.coutp != cs.cout:
-                        gview(cs.bnm.weight).copy_(v[6][:cs.cout])
-                        gview(cs.bnm.bias).copy_(v[7][:cs.cout])
-                        out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = gview(cs.bnm.weight), gview(cs.bnm.bias)
-                else:
-                    dy_ptr, dy_ld = g.ptr, g.ld
-                if cs.conv.bias is not None:
-                    db = gview(cs.conv.bias)
-                    call('ssp_colsum', dy_ptr, dy_ld, cs.M, cs.cout, db.data_ptr(), st)
-                    out_grads[id(cs.conv.bias)] = db
-                src = None if cs.first else producer_of(cs.inp)
-                # tail schedule: the consumer of the fused first block (layer 2) runs its data gradient - the head of the
-                # chain that ends the step - BEFORE its filter gradient is released on the side stream
-                owner = None if src is None else (self.convs.get(src - 1) if src in self.fused_pool else self.convs.get(src))
-                defer = tail_sched and owner is not None and owner.first_live
-                if defer:
-                    self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
-                side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
-                gw = gview(cs.conv.weight, cs.packed)
-                if cs.packed and getattr(cs, 'wgrad_wino', 0):
-                    wws = self._wino_ws(cs)
-                    call('ssp_conv_wgrad_wino_t', dy_ptr, None if getattr(cs, 'v_live', False) else cs.inp.ptr, gw.data_ptr(),
-                         B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(), wws.numel(), st2)
-                    cs.v_live = False
-                elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
-                    call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
-                         cs.inp.ld, cs.k, st2)
-                else:
-                    call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.H, cs.W, cs.cinp,
-                         cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
-                    call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
-                out_grads[id(cs.conv.weight)] = gw
-                if self.reducer is not None:
-                    with torch.cuda.stream(side):   # the all-reduce of a finished bucket is ordered after its wgrads
-                        self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
-                if not cs.first and not defer:
-                    self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
-            elif t == 'maxpool':
-                if ind not in written:
-                    continue
-                op = [o_ for o_ in self.ops_fwd if o_[0] in ('maxpool', 'maxpool_s1') and o_[1] == ind][0]
-                _, _, src, out = op
-                sind = producer_of(src)
-                gin = self._grad_buf(sind, src)
-                g = self.grads[ind]
-                call('ssp_maxpool_bwd' if op[0] == 'maxpool' else 'ssp_maxpool_s1_bwd', src.ptr, src.ld, g.ptr, g.ld,
-                     gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, 1 if sind in written else 0, st)
-                written.add(sind)
-            elif t == 'shortcut':
-                if ind not in written:
-                    continue
-                _, _, a, b, out, slope = [o_ for o_ in self.ops_fwd if o_[0] == 'shortcut' and o_[1] == ind][0]
-                ia, ib = producer_of(a), producer_of(b)
-                ga, gb = self._grad_buf(ia, a), self._grad_buf(ib, b)
-                g = self.grads[ind]
-                # (from = -1: ia == ib, one buffer - the kernel adds 2 g')
-                call('ssp_shortcut_bwd', g.ptr, g.ld, out.ptr, out.ld, ga.ptr, ga.ld, 1 if ia in written else 0, gb.ptr,
-                     gb.ld, 1 if ib in written else 0, _pad4(out.C), B * out.H * out.W, slope, st)
-                written.add(ia)
-                written.add(ib)
-            elif t in ('avgpool', 'softmax'):
-                if ind not in written:
-                    continue
-                _, _, src, out = [o_ for o_ in self.ops_fwd if o_[0] == t and o_[1] == ind][0]
-                sind = producer_of(src)
-                gin = self._grad_buf(sind, src)
-                g = self.grads[ind]
-                if t == 'avgpool':
-                    call('ssp_avgpool_bwd', g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W,
-                         1 if sind in written else 0, st)
-                else:
-                    call('ssp_softmax_bwd', out.ptr, out.ld, g.ptr, g.ld, gin.ptr, gin.ld, src.C, B * src.H * src.W,
-                         1 if sind in written else 0, st)
-                written.add(sind)
-            elif t == 'reorg':
-                if ind not in written:
-                    continue
-                op = [o_ for o_ in self.ops_fwd if o_[0] == 'reorg' and o_[1] == ind][0]
-                _, _, src, out = op
-                sind = producer_of(src)
-                gin = self._grad_buf(sind, src)
-                g = self.grads[ind]
-                call('ssp_reorg', g.ptr, g.ld, gin.ptr, gin.ld, src.C, B, src.H, src.W, 1,
-                     1 if sind in written else 0, st)
-                written.add(sind)
-            elif t == 'route':
-                if ind not in written:
-                    continue
-                layers = resolve_layers(block['layers'], ind)
-                g = self.grads[ind]
+        for op in reversed(self.ops):
+            if op.oind not in written:
+                continue          # nothing downstream of this block reaches the output
+            g = self.grads[op.oind]
+            kind = op.kind
+            if kind == 'conv':
+                self._conv_bwd(op, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched)
+            elif kind == 'shortcut':
+                a, b = op.srcs
+                ga, acc_a = grad_in(a)
+                gb, acc_b = (ga, acc_a) if b is a else grad_in(b)     # (from = -1: one buffer - the kernel adds 2 g')
+                out = op.out
+                call('ssp_shortcut_bwd', g.ptr, g.ld, out.ptr, out.ld, ga.ptr, ga.ld, acc_a, gb.ptr, gb.ld, acc_b,
+                     _pad4(out.C), B * out.H * out.W, op.slope, st)
+            elif kind in ('alias', 'concat'):
                 off = 0
-                for l in layers:
-                    a = self.acts[l]
-                    src = producer_of(a)
-                    gin = self._grad_buf(src, a)
-                    if gin is not g:
-                        call('ssp_copy_channels', _ptr(g.t, g.off + off), g.ld, gin.ptr, gin.ld, a.C, B * a.H * a.W,
-                             1 if src in written else 0, st)
-                    written.add(src)
+                for a in op.srcs:
+                    gin, acc = grad_in(a)
+                    call('ssp_copy_channels', _ptr(g.t, g.off + off), g.ld, gin.ptr, gin.ld, a.C, B * a.H * a.W, acc, st)
                     off += a.C
+            else:
+                src = op.srcs[0]
+                gin, acc = grad_in(src)
+                if kind in ('maxpool', 'maxpool_s1'):
+                    call('ssp_maxpool_bwd' if kind == 'maxpool' else 'ssp_maxpool_s1_bwd', src.ptr, src.ld, g.ptr, g.ld,
+                         gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, acc, st)
+                elif kind == 'reorg':
+                    call('ssp_reorg', g.ptr, g.ld, gin.ptr, gin.ld, src.C, B, src.H, src.W, 1, acc, st)
+                elif kind == 'avgpool':
+                    call('ssp_avgpool_bwd', g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, acc, st)
+                else:
+                    call('ssp_softmax_bwd', op.out.ptr, op.out.ld, g.ptr, g.ld, gin.ptr, gin.ld, src.C, B * src.H * src.W,
+                         acc, st)
         main.wait_stream(side)                  # every filter gradient is complete before autograd hands them out
         return out_grads
+
+    def _conv_bwd(self, cs, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched):
+        """Backward launches of conv block `cs` from the gradient g of its (pooled) output: BatchNorm / activation backward,
+        bias gradient, filter gradient on the side stream, data gradient into the producer of its input."""
+        B = self.B
+        call = _lib.call
+        st, st2 = main.cuda_stream, side.cuda_stream
+        training = self.was_training
+        v = cs.vec
+        if cs.first_live:
+            # first block, fused form: both backward passes recompute the convolution from the input
+            dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
+            out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
+            wptr = self._wbuf(cs).data_ptr()
+            call('ssp_first_bwd_reduce', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
+                 v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
+            call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
+                 1 if training else 0, 0, dgam.data_ptr(), dbet.data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
+            # The step's tail is a dependency chain: dgrad of the block's consumer -> this reduce -> this filter
+            # gradient (HBM-bound: it re-reads the 1.4 GB output gradient).  With the tail schedule the consumer's
+            # filter gradient (MFMA-bound) was held back behind its data gradient and is running on the side
+            # stream NOW: this pass stays on the main stream and overlaps it, instead of queueing behind it.
+            fst = st if tail_sched else st2
+            if not tail_sched:
+                side.wait_stream(main)
+            gw = gview(cs.conv.weight, False)
+            if cs.first_wpart is None:      # per-workgroup partial gradients, summed in float64
+                cs.first_wpart = torch.empty(_lib.query('ssp_first_wgrad_workspace_floats', B, cs.H, cs.W),
+                                             dtype=torch.float32, device=self.device)
+            call('ssp_first_bwd_wgrad', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
+                 v[0].data_ptr(), v[1].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), cs.slope,
+                 self._gbuf(cs).data_ptr(), cs.first_wpart.data_ptr(), cs.first_wpart.numel(), B, cs.H, cs.W, fst)
+            call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, fst)
+            out_grads[id(cs.conv.weight)] = gw
+            if self.reducer is not None:
+                if tail_sched:
+                    side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
+            return
+        if cs.needs_act:
+            if cs.bn and cs.coutp == cs.cout:
+                dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
+                out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
+                dg_ptr, db_ptr = dgam.data_ptr(), dbet.data_ptr()
+                # two-level reduction (per-workgroup partials -> fp64 finalize).  The single-pass form of
+                # ssp_bn_act_bwd (atomics into the zeroed gradient, no finalize launch) measured 1.1 ms SLOWER
+                # per step: 1024 workgroups hammering the same 2*C addresses serialise in the L2.
+                partial = self.bn_partial.data_ptr()
+            else:
+                dg_ptr, db_ptr = v[6].data_ptr(), v[7].data_ptr()
+                partial = self.bn_partial.data_ptr()
+            if cs.ind in fused_stats:
+                # the two reductions came out of the consumer's data-gradient launch: finalize + apply only
+                ptile, rows, folded = cs.bnp
+                call('ssp_bn_act_bwd_partials', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(),
+                     cs.ldraw, v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B,
+                     cs.H, cs.W, cs.slope, 1 if training else 0, ptile.data_ptr(), rows, 1 if folded else 0,
+                     dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+            else:
+                call('ssp_bn_act_bwd', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(), cs.ldraw,
+                     v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B, cs.H, cs.W,
+                     1 if cs.pool else 0, cs.slope, 1 if (training and cs.bn) else 0, partial,
+                     dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+            dy_ptr, dy_ld = cs.raw.data_ptr(), cs.ldraw
+            if cs.bn and cs.coutp != cs.cout:
+                gview(cs.bnm.weight).copy_(v[6][:cs.cout])
+                gview(cs.bnm.bias).copy_(v[7][:cs.cout])
+                out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = gview(cs.bnm.weight), gview(cs.bnm.bias)
+        else:
+            dy_ptr, dy_ld = g.ptr, g.ld
+        if cs.conv.bias is not None:
+            db = gview(cs.conv.bias)
+            call('ssp_colsum', dy_ptr, dy_ld, cs.M, cs.cout, db.data_ptr(), st)
+            out_grads[id(cs.conv.bias)] = db
+        src = None if cs.first else cs.inp.producer
+        # tail schedule: the consumer of the fused first block (layer 2) runs its data gradient - the head of the
+        # chain that ends the step - BEFORE its filter gradient is released on the side stream
+        owner = None if src is None else (self.convs.get(src - 1) if src in self.fused_pool else self.convs.get(src))
+        defer = tail_sched and owner is not None and owner.first_live
+        if defer:
+            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
+        side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
+        gw = gview(cs.conv.weight, cs.packed)
+        if cs.packed and cs.wgrad_wino:
+            wws = self._wino_ws(cs)
+            call('ssp_conv_wgrad_wino_t', dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(),
+                 B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(), wws.numel(), st2)
+            cs.v_live = False
+        elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
+            call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
+                 cs.inp.ld, cs.k, st2)
+        else:
+            call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.H, cs.W, cs.cinp,
+                 cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
+            call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
+        out_grads[id(cs.conv.weight)] = gw
+        if self.reducer is not None:
+            with torch.cuda.stream(side):   # the all-reduce of a finished bucket is ordered after its wgrads
+                self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
+        if not cs.first and not defer:
+            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
 
 
 class _DarknetFn(torch.autograd.Function):

@@ -63,15 +63,20 @@ def test_connected_modules_and_parameters():
     assert id(fc2.weight) in ids and id(fc2.bias) in ids
 
 
-def test_plan_pose_cfg():
+def test_plan_ops_pose_cfg():
     m = _model('pose')
     plan = _plan(m, 'pose')
-    kinds = [op[0] for op in plan.ops_fwd]
+    kinds = [op.kind for op in plan.ops]
     assert kinds.count('shortcut') == 3 and kinds.count('maxpool_s1') == 1
-    sc = {op[1]: op for op in plan.ops_fwd if op[0] == 'shortcut'}
+    sc = {op.ind: op for op in plan.ops if op.kind == 'shortcut'}
     assert sorted(sc) == [6, 9, 15]
-    assert [sc[i][5] for i in (6, 9, 15)] == [1.0, 0.1, 0.0]        # linear, leaky, relu
-    assert sc[15][2] is sc[15][3]                                    # from = -1: both summands are one map
+    assert [sc[i].slope for i in (6, 9, 15)] == [1.0, 0.1, 0.0]     # linear, leaky, relu
+    assert sc[15].srcs[0] is sc[15].srcs[1]                          # from = -1: both summands are one map
+    # the layers whose gradient buffers receive each map's gradient, resolved at plan construction
+    assert [a.producer for a in sc[6].srcs] == [3, 5]
+    assert [a.producer for a in sc[15].srcs] == [14, 14]
+    assert plan.convs[0].out.producer == 1                           # a fused pool's output belongs to the pool
+    assert plan.convs[4].inp.producer == 3
     # layer 3 (pool output) feeds conv 4 and shortcut 6; layer 6 feeds conv 7 and shortcut 9
     assert sorted(plan.consumers[3]) == [4, 6] and sorted(plan.consumers[6]) == [7, 9]
     assert plan.consumers[14] == [15, 15]
@@ -97,10 +102,10 @@ def test_plan_pose_cfg_bn_fusion_skips_shortcut_sources():
     assert fused == {5: 4}          # conv 4 -> conv 5 is the only single-consumer BN conv -> conv pair
 
 
-def test_plan_classifier_cfg():
+def test_plan_ops_classifier_cfg():
     m = _model('cls')
     plan = _plan(m, 'cls')
-    kinds = [op[0] for op in plan.ops_fwd]
+    kinds = [op.kind for op in plan.ops]
     assert kinds == ['conv', 'conv', 'conv', 'conv', 'avgpool', 'conv', 'conv', 'softmax']
     assert sorted(plan.convs) == [0, 2, 4, 5, 7, 8]
     fc1, fc2 = plan.convs[7], plan.convs[8]
