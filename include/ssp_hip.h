@@ -203,6 +203,14 @@ int ssp_first_bwd_wgrad(const float* x, const float* wt, const float* g, int ldg
                         const float* mean, const float* invstd, const float* c1, const float* c2, float slope, float* dw,
                         float* workspace, int64_t workspace_floats, int B, int H, int W, void* stream);
 int64_t ssp_first_wgrad_workspace_floats(int B, int H, int W);
+/*   bwd_dgrad : dx[B*H*W][4] = dL/dx, the gradient of the block's input: conv_transpose3x3(dy_raw, w) with dy_raw the
+ *               BatchNorm-backward of leaky'(pool-scatter(g)) (c1 / c2 from bwd_reduce + ssp_bn_bwd_finalize, as
+ *               bwd_wgrad); the padding channel is written as zero.  The full-resolution map and its gradient are
+ *               recomputed per tile (one-window border) and never stored; every element is written once by one thread,
+ *               no atomics: two calls give bitwise-equal results.  dx 16-byte aligned. */
+int ssp_first_bwd_dgrad(const float* x, const float* wt, const float* g, int ldg, const float* scale, const float* shift,
+                        const float* mean, const float* invstd, const float* c1, const float* c2, float slope, float* dx,
+                        int B, int H, int W, void* stream);
 
 /* ---- optimizer ------------------------------------------------------------------ */
 /* One torch.optim.SGD step (train.py:388,106) over a contiguous fp32 range of n values, in place:

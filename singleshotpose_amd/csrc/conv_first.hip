@@ -470,3 +470,207 @@ int ssp_first_bwd_wgrad_launch(const float* x, const float* wt, const float* g, 
   SSP_CHECK_LAUNCH("first_wgrad_finalize");
   return SSP_OK;
 }
+
+// ---- input gradient: dx = conv_transpose3x3(dy_raw, w), dy_raw = BN-backward-apply(leaky'(pool-scatter(g))) ----
+//
+// A workgroup owns a DG_T x DG_T pooled tile (2 DG_T x 2 DG_T raw pixels) of dx and recomputes dy_raw on the whole 2 x 2
+// pool windows of the tile plus a one-window border: (DG_T + 2) pooled rows x 8 pooled columns = (DG_T + 2) MFMA blocks of
+// the layout above (8 pooled pixels x 4 window positions x 32 channels), DG_T = 6.  The border is recompute overhead:
+// (8 / 6)^2 = 1.78x the tile's own convolution and dy products.  Per block:
+//   1. the convolution by first_conv (same A operands, same weights, same k order as the four passes above: bit-identical
+//      raw values, so the pool winners and leaky signs are the ones the forward and the reductions saw);
+//   2. dy_raw in registers (as MODE 3 forms dx), zero on pixels outside the image (padding of the transposed conv);
+//   3. dy_raw -> LDS (per-wave [32 px][33] slab), read back with the pixel on the A row and the channel on k:
+//      Z[px][j] = sum_co dy_raw[px][co] * w[co][j], j = tap * 3 + ci (27 of the 32 columns), 16 MFMAs 32x32x2;
+//   4. Z -> the workgroup's region image in LDS.
+// Then every dx pixel of the tile is the sum of nine Z values of its neighbours, dx[q][ci] = sum_t Z[q - off(t)][t][ci], in a
+// fixed order by one thread: each element is written once, no atomics, bitwise reproducible.
+constexpr int DG_T = 6;                         // pooled pixels per tile side
+constexpr int DG_RB = DG_T + 2;                 // region blocks (pooled rows), one pooled row of 8 windows each
+constexpr int DG_RW = 16;                       // region raw columns (8 windows)
+constexpr int DG_ZS = 27;                       // floats per region pixel in LDS (odd: conflict-free gather)
+constexpr int DG_TS = 33;                       // floats per pixel of the per-wave transpose slab
+
+struct FirstDgradArgs {
+  FirstArgs f;
+  float* dx;                                    // [B*H*W][4]
+  int ntx, nty;                                 // tiles per row / column
+  SspFastDiv div_ntx, div_nty;
+};
+
+__global__ void __launch_bounds__(256, 3) first_dgrad_kernel(FirstDgradArgs d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const FirstArgs& p = d.f;
+  __shared__ float zs[2 * DG_RB * DG_RW * DG_ZS];
+  __shared__ float ts[4][32 * DG_TS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, lh = lane >> 5;
+  const int pp = li & 7, q = li >> 3;
+  const int cout = li;
+  const int lane_pix_off = (q >> 1) * p.W + 2 * pp + (q & 1);
+
+  // tile decode: blockIdx.x = (b * nty + ty) * ntx + tx
+  const unsigned t1 = ssp_div((unsigned)blockIdx.x, d.div_ntx);
+  const int tx = (int)blockIdx.x - (int)t1 * d.ntx;
+  const unsigned bb = ssp_div(t1, d.div_nty);
+  const int ty = (int)(t1 - bb * (unsigned)d.nty), b = (int)bb;
+  const int Y0 = ty * DG_T, X0 = tx * DG_T;       // first pooled row / column of the tile
+  const int px0 = X0 - 1;                         // first pooled column of the region (all blocks)
+
+  float wreg[18];
+  first_load_weights(p, cout, lh, wreg);
+  // B operand of the Z product: step s feeds channel 2s + lh, column j = li = (tap, ci)
+  float wz[16];
+  {
+    const int jt = li / 3, jc = li - 3 * (li / 3);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) wz[s] = li < 27 ? p.wt[(2 * s + lh) * 36 + jt * 4 + jc] : 0.f;
+  }
+  const float sc = p.scale[cout], sh = p.shift[cout], mu = p.mean[cout], is = p.invstd[cout];
+  const float k1 = p.c1[cout], k2 = p.c2[cout];
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)FIRST_OOB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, (int)FIRST_OOB, 0x00020000);
+
+  // this wave's two region blocks: pooled rows Y0 - 1 + rb, rb = 2 * wid + {0, 1}; both fetched up front
+  u32x2 xa[2][9];
+  float gv[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int yo = Y0 - 1 + 2 * wid + i;
+    const bool border = (yo < 1) | (yo > p.Ho - 2) | (px0 < 1) | (px0 + 9 > p.Wo);
+    if (!border) {
+      const int base_pix = (b * p.H + 2 * yo) * p.W + 2 * px0;
+      const unsigned voff = (unsigned)(lane_pix_off * 16 + lh * 8);
+      const int sbase = __builtin_amdgcn_readfirstlane(base_pix) * 16;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int soff = sbase + ((t / 3 - 1) * p.W + (t % 3 - 1)) * 16;
+        xa[i][t] = __builtin_amdgcn_raw_buffer_load_b64(rs_x, voff, soff, 0);
+      }
+      const int pooled_u = __builtin_amdgcn_readfirstlane((b * p.Ho + yo) * p.Wo + px0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        gv[i][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, (unsigned)((4 * lh * p.ldg + cout) * 4),
+                                                                                  (pooled_u + c) * p.ldg * 4, 0));
+    } else {
+      const int y = 2 * yo + (q >> 1), x = 2 * px0 + 2 * pp + (q & 1);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        const bool ok = ((unsigned)yy < (unsigned)p.H) && ((unsigned)xx < (unsigned)p.W);
+        const unsigned voff = ok ? (unsigned)((((b * p.H + yy) * p.W + xx) * 4 + lh * 2) * 4) : FIRST_OOB;
+        xa[i][t] = __builtin_amdgcn_raw_buffer_load_b64(rs_x, voff, 0, 0);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int xo = px0 + 4 * lh + c;
+        const bool ok = ((unsigned)yo < (unsigned)p.Ho) && ((unsigned)xo < (unsigned)p.Wo);
+        const unsigned voff = ok ? (unsigned)((((b * p.Ho + yo) * p.Wo + xo) * p.ldg + cout) * 4) : FIRST_OOB;
+        gv[i][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, voff, 0, 0));
+      }
+    }
+  }
+
+  float* slab = ts[wid];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int rb = 2 * wid + i, yo = Y0 - 1 + rb;
+    const f32x16 acc = first_conv(xa[i], wreg);
+    // pool winner / leaky sign of this lane's 4 windows, exactly as first_block_kernel's backward modes
+    float dyv[4];
+    int sel[4];
+    bool inside[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float gvc = gv[i][c];
+      float y0 = acc[c] * sc + sh;
+      float best = y0 > 0.f ? y0 : y0 * p.slope, ybest = y0;
+      int s = 0;
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        const float y = acc[c + 4 * w] * sc + sh;
+        const float a = y > 0.f ? y : y * p.slope;
+        if (a > best) { best = a; ybest = y; s = w; }
+      }
+      dyv[c] = ybest > 0.f ? gvc : gvc * p.slope;
+      sel[c] = s;
+      const int xo = px0 + 4 * lh + c;
+      inside[c] = ((unsigned)yo < (unsigned)p.Ho) && ((unsigned)xo < (unsigned)p.Wo);
+    }
+    // dy_raw -> slab[row i = (r&3) + 8*(r>>2) + 4*lh][cout]
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = r & 3, w = r >> 2;
+      const float xh = (acc[r] - mu) * is;
+      const float dyq = (sel[c] == w) ? dyv[c] : 0.f;
+      const float dr = inside[c] ? sc * (dyq - k1 - xh * k2) : 0.f;
+      slab[((r & 3) + 8 * (r >> 2) + 4 * lh) * DG_TS + cout] = dr;
+    }
+    __syncthreads();
+    f32x16 z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) z = __builtin_amdgcn_mfma_f32_32x32x2f32(slab[li * DG_TS + 2 * s + lh], wz[s], z, 0, 0, 0);
+    // Z row i = q' * 8 + pp' -> region pixel (2 rb + (q' >> 1), 2 pp' + (q' & 1)); column j = li
+    if (li < 27) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int qq = row >> 3, pq = row & 7;
+        zs[((2 * rb + (qq >> 1)) * DG_RW + 2 * pq + (qq & 1)) * DG_ZS + li] = z[r];
+      }
+    }
+    __syncthreads();          // (the slab is rewritten by the next block)
+  }
+
+  // dx of the tile: raw pixel (u, v), u, v < 2 DG_T, is region pixel (u + 2, v + 2)
+  if (tid < 4 * DG_T * DG_T) {
+    const int u = tid / (2 * DG_T), v = tid - u * (2 * DG_T);
+    const int y = 2 * Y0 + u, x = 2 * X0 + v;
+    if (y < p.H && x < p.W) {
+      float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int ru = u + 2 - (t / 3 - 1), rv = v + 2 - (t % 3 - 1);
+        const float* zp = &zs[(ru * DG_RW + rv) * DG_ZS + t * 3];
+        o0 += zp[0];
+        o1 += zp[1];
+        o2 += zp[2];
+      }
+      float4 o;
+      o.x = o0; o.y = o1; o.z = o2; o.w = 0.f;
+      *reinterpret_cast<float4*>(d.dx + ((int64_t)(b * p.H + y) * p.W + x) * 4) = o;
+    }
+  }
+#endif
+}
+
+int ssp_first_bwd_dgrad_launch(const float* x, const float* wt, const float* g, int ldg, const float* scale,
+                               const float* shift, const float* mean, const float* invstd, const float* c1,
+                               const float* c2, float slope, float* dx, int B, int H, int W, hipStream_t stream) {
+  if (int rc = first_check(x, wt, B, H, W, "first_bwd_dgrad")) return rc;
+  SSP_CHECK_ARG(g != nullptr && ldg >= FIRST_COUT && (int64_t)B * (H / 2) * (W / 2) * ldg * 4 < (1ll << 31),
+                "first_bwd_dgrad: bad gradient (ldg >= 32, < 2 GiB)");
+  SSP_CHECK_ARG(scale != nullptr && shift != nullptr && mean != nullptr && invstd != nullptr && c1 != nullptr && c2 != nullptr,
+                "first_bwd_dgrad: null BatchNorm vector");
+  SSP_CHECK_ARG(dx != nullptr && (((uintptr_t)dx) & 15) == 0, "first_bwd_dgrad: dx must be 16-byte aligned");
+  FirstDgradArgs d;
+  d.f = first_args(x, wt, B, H, W, 1);
+  FirstArgs& a = d.f;
+  a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd; a.c1 = c1; a.c2 = c2; a.slope = slope;
+  a.g = g; a.ldg = ldg;
+  d.dx = dx;
+  d.ntx = ssp_cdiv(a.Wo, DG_T);
+  d.nty = ssp_cdiv(a.Ho, DG_T);
+  d.div_ntx = ssp_fastdiv((unsigned)d.ntx);
+  d.div_nty = ssp_fastdiv((unsigned)d.nty);
+  const int64_t nwg = (int64_t)B * d.nty * d.ntx;
+  SSP_CHECK_ARG(nwg < (1ll << 31), "first_bwd_dgrad: too many tiles");
+  // algorithmic FLOPs of the transposed convolution (3 real input channels), as the filter gradient books its own
+  SspProfScope prof(SSP_PROF_FIRST_BWD, stream, 2.0 * (double)B * H * W * FIRST_COUT * 27.0);
+  hipLaunchKernelGGL(first_dgrad_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, d);
+  SSP_CHECK_LAUNCH("first_bwd_dgrad");
+  return SSP_OK;
+}

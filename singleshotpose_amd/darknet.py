@@ -272,14 +272,16 @@ class Darknet(nn.Module):
         else:
             if x.dim() != 4 or x.size(1) != nc:
                 raise ValueError("expected a (B,%d,H,W) input" % nc)
-            x = x.detach().to(torch.float32).contiguous()
+            # (not detached: with x.requires_grad the cast and the copy stay in the graph, so x.grad arrives in x's own
+            # dtype and shape)
+            x = x.to(torch.float32).contiguous()
             shape = (x.size(0), x.size(2), x.size(3))
         params = self._params()
         for p in params:
             if p.device != x.device:
                 raise RuntimeError("model parameters are on %s but the input is on %s - call model.cuda()" % (p.device, x.device))
         plan = self._plan(shape, x.device)
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         if need_grad and self.training:
             return _DarknetFn.apply(plan, True, x, *params)
         if need_grad:

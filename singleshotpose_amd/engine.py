@@ -203,7 +203,7 @@ class _Act(object):
 
     producer: the layer whose gradient buffer (Plan.grads) receives this map's gradient - the FIRST layer whose forward
     output it is (Plan._place): a fused 2x2 pool's output belongs to the pool, a one-layer route (or a region block) passes
-    its source's map on and keeps its producer; None for the network input.  flat: the reference holds this map as a 2-D
+    its source's map on and keeps its producer; INPUT (-1) for the network input.  flat: the reference holds this map as a 2-D
     (B, C) tensor (avgpool, connected, and softmax / shortcut / route of those)."""
     __slots__ = ('t', 'off', 'C', 'H', 'W', 'ld', 'flat', 'producer')
 
@@ -215,6 +215,9 @@ class _Act(object):
     @property
     def ptr(self):
         return _ptr(self.t, self.off)
+
+
+INPUT = -1      # Plan.grads key (and _Act.producer) of the network input's gradient
 
 
 class _Op(object):
@@ -309,7 +312,10 @@ class Plan(object):
         self.in_c = in_c
         self.in_cp = _pad4(in_c)
         self.x_nhwc = torch.empty(B * H * W * self.in_cp, **f32)
-        self.input_act = _Act(self.x_nhwc, 0, self.in_cp, H, W, self.in_cp)
+        # (C = the real channel count: a first block that reads C - reorg, softmax - must not see the padding channel)
+        self.input_act = _Act(self.x_nhwc, 0, in_c, H, W, self.in_cp)
+        self.input_act.producer = INPUT
+        self._dpack_in = None     # first conv's data-gradient operand [in_cp][k*k][coutp]: only plans asked for dL/dx
 
         self.convs = {}      # layer index -> _ConvSpec
         self.fused_pool = set()   # maxpool layers folded into the preceding conv block
@@ -398,6 +404,8 @@ class Plan(object):
             elif t == 'reorg':
                 if int(block['stride']) != 2:
                     raise NotImplementedError("reorg stride != 2")
+                if prev.C % 4:
+                    raise NotImplementedError("reorg of a %d-channel map (ssp_reorg needs a multiple of 4)" % prev.C)
                 op = _Op('reorg', ind, [prev], _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c))
             elif t == 'shortcut':
                 f = resolve_layers(block['from'], ind)[0]
@@ -1580,9 +1588,15 @@ class Plan(object):
                  self.ws_floats, st)
         written.add(src)
 
-    def backward(self, grad_out):
-        """grad_out: (B, C, h, w) NCHW, or (B, C) when the network ends in avgpool / connected / softmax.  Returns {param
-        tensor id: grad tensor}."""
+    def backward(self, grad_out, want_input=False, want_params=True):
+        """grad_out: (B, C, h, w) NCHW, or (B, C) when the network ends in avgpool / connected / softmax.  Returns
+        ({param tensor id: grad tensor}, dL/dx as (B, in_c, H, W) fp32 or None).
+
+        want_input: also compute the gradient of the network input.  want_params=False (only with want_input): the
+        input-only backward - the data-gradient chain and the BatchNorm-backward reductions it needs, no filter / bias /
+        BatchNorm-parameter gradients, no flat gradient buffer, no reducer call; the dict is empty."""
+        if not (want_input or want_params):
+            raise ValueError("Plan.backward: neither the input nor the parameter gradients are wanted")
         if self.consumed:
             raise RuntimeError("Darknet backward called twice on the same forward: the HIP path rewrites the saved "
                                "conv outputs in place (no retain_graph support)")
@@ -1600,6 +1614,8 @@ class Plan(object):
             raise NotImplementedError("network output channels must be a multiple of 4")
         if self.side_stream is None:
             self.side_stream = _side_stream(self.device)
+        if not want_params:
+            return self._backward_body(None, want_input)
         # ONE flat gradient buffer per model and device, reused by every backward of every plan (the layout depends on the
         # model only): the returned gradients are views of it.  Reuse is safe only while nothing else still views the
         # buffer (optimizer.zero_grad(set_to_none=True) - torch's default - drops the .grad views; a caller that keeps or
@@ -1614,19 +1630,21 @@ class Plan(object):
             self.net._flat_grads[self.device] = (flat, _storage_refs(flat))
         flat.record_stream(self.side_stream)
         self.last_flat_grad = flat
-        return self._backward_body(flat)
+        return self._backward_body(flat, want_input)
 
-    def _backward_body(self, flat):
+    def _backward_body(self, flat, want_input):
+        """flat None: input-only backward (see backward)."""
         B = self.B
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
         written = set()
         fused_stats = set()      # blocks whose BatchNorm-backward reductions were produced by their consumer's dgrad launch
         written.add(self.last)
-        flat.zero_()
-        for cs in self.convs.values():          # gradient staging of the parameters that are not channels-last
-            if not cs.packed and not cs.first_live:      # (the fused first block's filter gradient is WRITTEN, not accumulated)
-                self._gbuf(cs).zero_()
+        if flat is not None:
+            flat.zero_()
+            for cs in self.convs.values():          # gradient staging of the parameters that are not channels-last
+                if not cs.packed and not cs.first_live:      # (the fused first block's filter gradient is WRITTEN, not accumulated)
+                    self._gbuf(cs).zero_()
         # Filter gradients run on a second stream: wgrad(l) only needs dY(l) and the saved input activation, so it
         # overlaps the dgrad(l) -> BN-backward(l-1) chain of the main stream and fills the idle CUs of its last wave.
         main = torch.cuda.current_stream()
@@ -1641,7 +1659,7 @@ class Plan(object):
                     self._repack_dgrad(cs, main)
         out_grads = {}
         tail_sched = side is not main and os.environ.get('SSP_TAIL_SCHED', '1') != '0'
-        if self.reducer is not None:
+        if self.reducer is not None and flat is not None:
             self.reducer.begin(flat)
 
         def gview(prm, channels_last=False):
@@ -1663,7 +1681,7 @@ class Plan(object):
             g = self.grads[op.oind]
             kind = op.kind
             if kind == 'conv':
-                self._conv_bwd(op, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched)
+                self._conv_bwd(op, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched, want_input)
             elif kind == 'shortcut':
                 a, b = op.srcs
                 ga, acc_a = grad_in(a)
@@ -1690,17 +1708,39 @@ class Plan(object):
                 else:
                     call('ssp_softmax_bwd', op.out.ptr, op.out.ld, g.ptr, g.ld, gin.ptr, gin.ld, src.C, B * src.H * src.W,
                          acc, st)
-        main.wait_stream(side)                  # every filter gradient is complete before autograd hands them out
-        return out_grads
+        dx = None
+        if want_input:
+            # NHWC [B*H*W][in_cp] -> the (B, C, H, W) input gradient
+            o = self.input_act
+            dx = torch.empty(B, self.in_c, self.H, self.W, dtype=torch.float32, device=self.device)
+            if INPUT in written:
+                call('ssp_nhwc_to_nchw', self.grads[INPUT].ptr, dx.data_ptr(), B, self.in_c, o.H, o.W, o.ld, st)
+            else:
+                dx.zero_()          # no path from the input reaches the output
+        if flat is not None:
+            main.wait_stream(side)              # every filter gradient is complete before autograd hands them out
+        return out_grads, dx
 
-    def _conv_bwd(self, cs, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched):
+    def _conv_bwd(self, cs, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched, want_input):
         """Backward launches of conv block `cs` from the gradient g of its (pooled) output: BatchNorm / activation backward,
-        bias gradient, filter gradient on the side stream, data gradient into the producer of its input."""
+        bias gradient, filter gradient on the side stream, data gradient into the producer of its input (for the first
+        block: into the input's gradient buffer, when want_input).  flat None: input-only backward, no parameter
+        gradient work."""
         B = self.B
         call = _lib.call
         st, st2 = main.cuda_stream, side.cuda_stream
         training = self.was_training
         v = cs.vec
+        params = flat is not None
+        if cs.first_live and not params:
+            # input-only, fused first block: the reductions dy_raw needs (dgamma / dbeta land in scratch), then dL/dx
+            wptr = self._wbuf(cs).data_ptr()
+            call('ssp_first_bwd_reduce', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
+                 v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
+            call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
+                 1 if training else 0, 0, v[6].data_ptr(), v[7].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
+            self._first_input_dgrad(cs, g, written, st)
+            return
         if cs.first_live:
             # first block, fused form: both backward passes recompute the convolution from the input
             dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
@@ -1710,6 +1750,8 @@ class Plan(object):
                  v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
             call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
                  1 if training else 0, 0, dgam.data_ptr(), dbet.data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
+            if want_input:          # main stream, after the finalize: it reads what the filter gradient below reads
+                self._first_input_dgrad(cs, g, written, st)
             # The step's tail is a dependency chain: dgrad of the block's consumer -> this reduce -> this filter
             # gradient (HBM-bound: it re-reads the 1.4 GB output gradient).  With the tail schedule the consumer's
             # filter gradient (MFMA-bound) was held back behind its data gradient and is running on the side
@@ -1733,7 +1775,7 @@ class Plan(object):
                     self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
             return
         if cs.needs_act:
-            if cs.bn and cs.coutp == cs.cout:
+            if cs.bn and cs.coutp == cs.cout and params:
                 dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
                 out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
                 dg_ptr, db_ptr = dgam.data_ptr(), dbet.data_ptr()
@@ -1757,12 +1799,19 @@ class Plan(object):
                      1 if cs.pool else 0, cs.slope, 1 if (training and cs.bn) else 0, partial,
                      dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
             dy_ptr, dy_ld = cs.raw.data_ptr(), cs.ldraw
-            if cs.bn and cs.coutp != cs.cout:
+            if cs.bn and cs.coutp != cs.cout and params:
                 gview(cs.bnm.weight).copy_(v[6][:cs.cout])
                 gview(cs.bnm.bias).copy_(v[7][:cs.cout])
                 out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = gview(cs.bnm.weight), gview(cs.bnm.bias)
         else:
             dy_ptr, dy_ld = g.ptr, g.ld
+        if not params:
+            # input-only: the data-gradient chain alone
+            if cs.first:
+                self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
+            else:
+                self._dgrad(cs, cs.inp.producer, dy_ptr, dy_ld, written, fused_stats, st)
+            return
         if cs.conv.bias is not None:
             db = gview(cs.conv.bias)
             call('ssp_colsum', dy_ptr, dy_ld, cs.M, cs.cout, db.data_ptr(), st)
@@ -1794,6 +1843,43 @@ class Plan(object):
                 self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
         if not cs.first and not defer:
             self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
+        elif cs.first and want_input:
+            self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
+
+    def _input_gbuf(self, written):
+        """The input's gradient buffer, NHWC [B*H*W][in_cp], and whether a launch accumulates into it (marks it written)."""
+        gin = self._grad_buf(INPUT, self.input_act)
+        acc = 1 if INPUT in written else 0
+        written.add(INPUT)
+        return gin, acc
+
+    def _input_dgrad(self, cs, dy_ptr, dy_ld, written, st):
+        """dL/dx of an un-fused first conv: ssp_conv_dgrad into the 4-channel input gradient (Cin_dx = in_cp; the operand's
+        padding rows stay zero, so the padding channel is written as zero).  The operand is built here, on first use - a
+        plan that is never asked for an input gradient neither holds nor repacks it."""
+        call = _lib.call
+        if self._dpack_in is None:
+            self._dpack_in = torch.zeros(self.in_cp * cs.k * cs.k * cs.coutp, dtype=torch.float32, device=self.device)
+        src = cs.conv.weight.detach()
+        if not cs.packed:
+            src = src.contiguous()
+        call('ssp_repack_dgrad_packed' if cs.packed else 'ssp_repack_dgrad', src.data_ptr(), self._dpack_in.data_ptr(),
+             cs.cout, cs.cin, cs.coutp, cs.k, st)
+        gin, acc = self._input_gbuf(written)
+        # plan 0: the library's heuristic (the tuner never times this launch); no split-K workspace is needed at K = 9 * Cout
+        call('ssp_conv_dgrad', dy_ptr, self._dpack_in.data_ptr(), gin.ptr, self.B, cs.H, cs.W, cs.coutp, self.in_cp,
+             dy_ld, gin.ld, cs.k, acc, 0, None, 0, st)
+
+    def _first_input_dgrad(self, cs, g, written, st):
+        """dL/dx of the fused first block (ssp_first_bwd_dgrad): recomputes the convolution per tile, never stores it."""
+        gin, acc = self._input_gbuf(written)
+        if acc:
+            raise NotImplementedError("the network input feeds the fused first block and another block: its gradient "
+                                      "would need an accumulating ssp_first_bwd_dgrad")
+        v = cs.vec
+        _lib.call('ssp_first_bwd_dgrad', cs.inp.ptr, self._wbuf(cs).data_ptr(), g.ptr, g.ld, v[2].data_ptr(),
+                  v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), cs.slope, gin.ptr,
+                  self.B, cs.H, cs.W, st)
 
 
 class _DarknetFn(torch.autograd.Function):
@@ -1816,14 +1902,16 @@ class _DarknetFn(torch.autograd.Function):
         if plan.generation != ctx.generation:
             raise RuntimeError("Darknet backward after a newer forward on the same input shape: the plan's saved "
                                "activations were overwritten")
-        grads = plan.backward(grad_out.contiguous())
+        want_x = ctx.needs_input_grad[2]
+        want_p = any(ctx.needs_input_grad[3:])
+        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p or not want_x)
         # Until its backward has run the node keeps its plan alive (forward at shape A, forward at shape B, backward of A
         # works whatever the cache evicted).  Afterwards only the cache does: a caller that still holds the loss tensor of the
         # previous resolution (every training loop does, until it assigns the next one) must not keep that resolution's
         # 30 - 65 GB of buffers next to the new plan's - that pair was the peak of the multi-scale soak.
         ctx.plan_ref = weakref.ref(plan)
         ctx.plan = None
-        res = [None, None, None]
+        res = [None, None, dx]
         for p in ctx.params:
             res.append(grads.get(id(p)))
         return tuple(res)
@@ -1850,8 +1938,10 @@ class _DarknetEvalFn(torch.autograd.Function):
         if ctx.x._version != ctx.xver:
             raise RuntimeError("Darknet (eval mode) backward: the input tensor was modified in place after the forward")
         plan.forward(ctx.x, False, need_grad=True)      # recompute, keeping the raw conv outputs
-        grads = plan.backward(grad_out.contiguous())
-        res = [None, None]
+        want_x = ctx.needs_input_grad[1]
+        want_p = any(ctx.needs_input_grad[2:])
+        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p or not want_x)
+        res = [None, dx]
         for p in ctx.params:
             res.append(grads.get(id(p)))
         return tuple(res)

@@ -1,0 +1,431 @@
+"""Gradient of the network input, dL/dx (x.requires_grad_(True)): the fused first-block kernel ssp_first_bwd_dgrad through
+the C ABI against float64 autograd on the CPU, and whole networks against the CPU oracle - training and eval mode, the
+input-only backward (every parameter frozen), first blocks that are not a conv, dtypes and resolutions."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from helpers import GOLD, ROOT, clone_state, load_state_into, make_targets, rel_err
+
+pytestmark = pytest.mark.gpu
+TOL = 3e-4
+YOLO = os.path.join(ROOT, 'cfg', 'yolo-pose.cfg')
+TINY = os.path.join(GOLD, 'tiny-pose.cfg')
+
+
+# ---------------------------------------------------------------------------------------------------- kernel
+@pytest.mark.parametrize("B,H,W", [(3, 32, 48), (3, 64, 64), (1, 416, 416)])
+def test_first_bwd_dgrad_kernel(B, H, W):
+    import gpu_util as G
+    from singleshotpose_amd import _lib
+    rs = np.random.RandomState(B * 7 + H + W)
+    x = torch.from_numpy(rs.uniform(0, 1, (B, 3, H, W)).astype(np.float32))
+    w = torch.from_numpy((rs.standard_normal((32, 3, 3, 3)) * 0.4).astype(np.float32))
+    gamma = torch.from_numpy(rs.uniform(0.5, 1.5, 32).astype(np.float32))
+    beta = torch.from_numpy((rs.standard_normal(32) * 0.2).astype(np.float32))
+    gpool = torch.from_numpy(rs.standard_normal((B, 32, H // 2, W // 2)).astype(np.float32))
+    st = G.stream()
+    M = B * H * W
+    xp = torch.zeros(B, 4, H, W)
+    xp[:, :3] = x
+    xdev = G.to_nhwc(xp)
+    wdev = G.pack_fwd(w, 4)
+    groups = _lib.query('ssp_first_groups', B, H, W)
+    tile = _lib.query('ssp_first_tile_pixels')
+    stats = torch.empty(groups * 64, device=G.dev())
+    _lib.call('ssp_first_fwd_stats', xdev.data_ptr(), wdev.data_ptr(), stats.data_ptr(), B, H, W, st)
+    vec = torch.zeros(8, 32, device=G.dev())
+    gdev, bdev = gamma.to(G.dev()), beta.to(G.dev())
+    rmean, rvar = torch.zeros(32, device=G.dev()), torch.ones(32, device=G.dev())
+    _lib.call('ssp_bn_fwd_finalize', stats.data_ptr(), groups, tile, M, 32, gdev.data_ptr(), bdev.data_ptr(),
+              rmean.data_ptr(), rvar.data_ptr(), 0.1, 1e-4, vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
+              vec[3].data_ptr(), st)
+    ldg = 40
+    gd = G.to_nhwc(gpool, ldg)
+    partial = torch.empty(groups * 64, device=G.dev())
+    _lib.call('ssp_first_bwd_reduce', xdev.data_ptr(), wdev.data_ptr(), gd.data_ptr(), ldg, vec[2].data_ptr(),
+              vec[3].data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), 0.1, partial.data_ptr(), B, H, W, st)
+    _lib.call('ssp_bn_bwd_finalize', partial.data_ptr(), groups, 32, M, 1, 0, vec[6].data_ptr(), vec[7].data_ptr(),
+              vec[4].data_ptr(), vec[5].data_ptr(), st)
+    raw = torch.empty(M, 32, device=G.dev())
+    _lib.call('ssp_first_conv_raw', xdev.data_ptr(), wdev.data_ptr(), raw.data_ptr(), 32, B, H, W, st)
+    outs = []
+    for _ in range(2):
+        dx = torch.full((M, 4), float('nan'), device=G.dev())       # every element written: NaN-poisoned
+        _lib.call('ssp_first_bwd_dgrad', xdev.data_ptr(), wdev.data_ptr(), gd.data_ptr(), ldg, vec[2].data_ptr(),
+                  vec[3].data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[4].data_ptr(), vec[5].data_ptr(), 0.1,
+                  dx.data_ptr(), B, H, W, st)
+        outs.append(dx.cpu())
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1])                               # deterministic, bit for bit
+    assert float(outs[0][:, 3].abs().max()) == 0.0                     # the padding channel is written as zero
+    # float64 reference with the kernel's own raw values (same pool winners / leaky signs)
+    xd = x.double().requires_grad_(True)
+    conv = F.conv2d(xd, w.double(), None, padding=1)
+    raw64 = G.from_nhwc(raw, B, 32, H, W).double()
+    r = raw64 + (conv - conv.detach())
+    out = F.max_pool2d(F.leaky_relu(F.batch_norm(r, None, None, gamma.double(), beta.double(), True, 0.1, 1e-4), 0.1), 2, 2)
+    out.backward(gpool.double())
+    got = outs[0][:, :3].reshape(B, H, W, 3).permute(0, 3, 1, 2)
+    assert rel_err(got.numpy(), xd.grad.numpy()) < 1e-4
+
+
+# ---------------------------------------------------------------------------------------------------- networks
+def _cfg_with_region(tmp_path, name, body, channels=3):
+    """A cfg: [net] + body + the region block of tiny-pose.cfg."""
+    text = open(TINY).read()
+    net = text[:text.index('[convolutional]')].replace('channels=3', 'channels=%d' % channels)
+    region = text[text.rindex('[region]'):]
+    p = str(tmp_path / name)
+    with open(p, 'w') as f:
+        f.write(net + body + '\n' + region)
+    return p
+
+
+def _model(cfg, seed=3):
+    from oracle.darknet_ref import seeded_state
+    from singleshotpose_amd.darknet import Darknet
+    model = Darknet(cfg)
+    state = seeded_state(model.blocks, seed)
+    load_state_into(model, model.blocks, state)
+    return model.cuda(), state
+
+
+def _decisions(model, B, H, W):
+    """The product's own raw conv outputs, leaky signs and pool winners of the training forward that just ran (call before
+    backward: it rewrites the raw outputs in place), as forward_ref's raw_override / act_override / pool_override - the
+    oracle/step_check.py recipe.  Independent fp32 and float64 forwards flip a handful of pool winners and leaky signs, and
+    a flip moves an input-gradient element by far more than rounding does."""
+    from singleshotpose_amd import _lib
+    plan = model._plans[(B, H, W, 0)]
+    st = torch.cuda.current_stream().cuda_stream
+    raws, acts, pools = {}, {}, {}
+    for ind, cs in plan.convs.items():
+        if cs.first_live:
+            r = torch.empty(cs.M * cs.cout, dtype=torch.float32, device='cuda')
+            _lib.call('ssp_first_conv_raw', cs.inp.ptr, plan._wbuf(cs).data_ptr(), r.data_ptr(), cs.cout, B, cs.H, cs.W, st)
+            ld = cs.cout
+        else:
+            r, ld = cs.raw, cs.ldraw
+        raws[ind] = r.view(-1)[:B * cs.H * cs.W * ld].view(B, cs.H, cs.W, ld)[..., :cs.cout].permute(0, 3, 1, 2).cpu()
+        if not (cs.needs_act and cs.slope == 0.1):
+            continue
+        a = torch.empty(cs.M * ld, dtype=torch.float32, device='cuda')
+        v = cs.vec
+        _lib.call('ssp_bn_act_fwd', r.data_ptr(), ld, a.data_ptr(), ld, v[2].data_ptr(), v[3].data_ptr(), ld, B, cs.H, cs.W,
+                  0, cs.slope, st)
+        a = a.view(B, cs.H, cs.W, ld)[..., :cs.cout].permute(0, 3, 1, 2).contiguous().cpu()
+        acts[ind] = a
+        if cs.pool:
+            pools[ind + 1] = F.max_pool2d(a, 2, 2, return_indices=True)[1]
+    return dict(raw_override={k: v.double() for k, v in raws.items()}, act_override=acts, pool_override=pools)
+
+
+def _oracle_input_grad(model, state, x, probe, training, frozen=None):
+    from oracle.darknet_ref import forward_ref
+    xr = x.detach().cpu().double().requires_grad_(True)
+    st = [None if e is None else {k: v.double() for k, v in e.items()} for e in clone_state(state)]
+    y = forward_ref(model.blocks, st, xr, training=training, **(frozen or {}))
+    y.backward(probe.double())
+    return xr.grad.numpy()
+
+
+def _probe(y, seed=5):
+    return torch.from_numpy(np.random.RandomState(seed).standard_normal(tuple(y.shape)).astype(np.float32))
+
+
+@pytest.mark.parametrize('cfg,B,H,W', [(TINY, 2, 96, 96), (YOLO, 2, 128, 96)])
+def test_network_input_grad_training(cfg, B, H, W):
+    model, state = _model(cfg)
+    model.train()
+    x = torch.from_numpy(np.random.RandomState(1).uniform(0, 1, (B, 3, H, W)).astype(np.float32))
+    xg = x.cuda().requires_grad_(True)
+    y = model(xg)
+    frozen = _decisions(model, B, H, W)
+    probe = _probe(y)
+    (y * probe.cuda()).sum().backward()
+    assert xg.grad is not None and xg.grad.shape == xg.shape and xg.grad.dtype == torch.float32
+    assert all(p.grad is not None for p in model.parameters())
+    ref = _oracle_input_grad(model, state, x, probe, True, frozen)
+    assert rel_err(xg.grad.cpu().numpy(), ref) < TOL
+
+
+def test_network_input_grad_region_loss():
+    from oracle.darknet_ref import forward_ref
+    from oracle.region_loss_ref import region_loss_ref
+    from singleshotpose_amd.region_loss import RegionLoss
+    model, state = _model(TINY)
+    model.train()
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.uniform(0, 1, (2, 3, 96, 96)).astype(np.float32))
+    tgt = torch.from_numpy(make_targets(rs, 2, [1, 1]))
+    xg = x.cuda().requires_grad_(True)
+    crit = RegionLoss()
+    crit.verbose = False
+    loss = crit(model(xg), tgt, 20)
+    loss.backward()
+    xr = x.double().requires_grad_(True)
+    st = [None if e is None else {k: v.double() for k, v in e.items()} for e in clone_state(state)]
+    y = forward_ref(model.blocks, st, xr, training=True)
+    r = region_loss_ref(y.detach().float(), tgt, 20)
+    y.backward(torch.as_tensor(r['grad']).double())
+    assert rel_err(xg.grad.cpu().numpy(), xr.grad.numpy()) < TOL
+
+
+def _ref_generic(model, x, training):
+    """CPU float64 forward of a cfg with shortcut / stride-1 maxpool / avgpool / softmax / connected blocks, on a copy of
+    the module tree (darknet.py's forward, the reference's block semantics)."""
+    from oracle.darknet_ref import reorg_ref
+    from singleshotpose_amd.cfg import resolve_layers
+    mods = copy.deepcopy(model.models).cpu().double()
+    mods.train(training)
+    outputs = {}
+    for ind, b in enumerate(model.blocks[1:]):
+        t = b['type']
+        if t == 'convolutional':
+            x = mods[ind](x)
+        elif t == 'maxpool':
+            s = int(b['stride'])
+            x = F.max_pool2d(x, int(b['size']), s) if s > 1 else F.max_pool2d(F.pad(x, (0, 1, 0, 1), mode='replicate'), 2, 1)
+        elif t == 'avgpool':
+            x = x.mean(dim=(2, 3))
+        elif t == 'softmax':
+            x = F.softmax(x, 1)
+        elif t == 'connected':
+            m = mods[ind]
+            lin = m[0] if isinstance(m, torch.nn.Sequential) else m
+            x = F.linear(x.view(x.size(0), -1), lin.weight, lin.bias)
+            if isinstance(m, torch.nn.Sequential):
+                x = F.leaky_relu(x, 0.1) if isinstance(m[1], torch.nn.LeakyReLU) else F.relu(x)
+        elif t == 'reorg':
+            x = reorg_ref(x, int(b['stride']))
+        elif t == 'route':
+            ls = resolve_layers(b['layers'], ind)
+            x = outputs[ls[0]] if len(ls) == 1 else torch.cat([outputs[l] for l in ls], 1)
+        elif t == 'shortcut':
+            x = outputs[resolve_layers(b['from'], ind)[0]] + outputs[ind - 1]
+            if b['activation'] == 'leaky':
+                x = F.leaky_relu(x, 0.1)
+            elif b['activation'] == 'relu':
+                x = F.relu(x)
+        elif t in ('region', 'cost'):
+            continue
+        outputs[ind] = x
+    return x
+
+
+@pytest.mark.parametrize('cfg,B,H,W', [('generic-pose.cfg', 2, 80, 80), ('generic-cls.cfg', 4, 64, 64)])
+def test_generic_cfg_input_grad(cfg, B, H, W):
+    from singleshotpose_amd.darknet import Darknet
+    model = Darknet(os.path.join(GOLD, cfg))
+    torch.manual_seed(0)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.1)
+    model = model.cuda().train()
+    x = torch.from_numpy(np.random.RandomState(2).uniform(0, 1, (B, 3, H, W)).astype(np.float32))
+    xg = x.cuda().requires_grad_(True)
+    y = model(xg)
+    probe = _probe(y)
+    (y * probe.cuda()).sum().backward()
+    xr = x.double().requires_grad_(True)
+    yr = _ref_generic(model, xr, True)
+    assert rel_err(y.detach().cpu().numpy(), yr.detach().numpy()) < 1e-4
+    yr.backward(probe.double())
+    assert rel_err(xg.grad.cpu().numpy(), xr.grad.numpy()) < TOL
+
+
+def _record(monkeypatch):
+    from singleshotpose_amd import _lib
+    log = []
+    orig = _lib.call
+
+    def rec(name, *args):
+        log.append(name)
+        return orig(name, *args)
+    monkeypatch.setattr(_lib, 'call', rec)
+    return log
+
+
+def _is_subsequence(a, b):
+    it = iter(b)
+    return all(any(n == m for m in it) for n in a)
+
+
+@pytest.mark.parametrize('cfg,B,H,W,extra', [
+    (TINY, 2, 96, 96, ['ssp_repack_dgrad', 'ssp_conv_dgrad', 'ssp_nhwc_to_nchw']),
+    (YOLO, 2, 64, 64, ['ssp_first_bwd_dgrad', 'ssp_nhwc_to_nchw'])])
+def test_same_step_with_and_without_input_grad(monkeypatch, cfg, B, H, W, extra):
+    model, _ = _model(cfg)
+    model.train()
+    x = torch.from_numpy(np.random.RandomState(4).uniform(0, 1, (B, 3, H, W)).astype(np.float32)).cuda()
+
+    def step(want_x):
+        model.zero_grad(set_to_none=True)
+        xi = x.clone().requires_grad_(want_x)
+        y = model(xi)
+        (y * _probe(y).cuda()).sum().backward()
+        torch.cuda.synchronize()
+        return [p.grad.detach().clone() for p in model.parameters()], xi.grad
+
+    step(False)                       # plan construction, tuning, first-batch bookkeeping
+    step(True)                        # ... and the input-gradient operand
+    log = _record(monkeypatch)
+    g0, xg0 = step(False)
+    plain = list(log)
+    del log[:]
+    g1, xg1 = step(True)
+    with_x = list(log)
+    del log[:]
+    assert xg0 is None and xg1 is not None
+    # the filter gradients of the generic kernels sum with fp32 atomics: two identical steps already differ in the last
+    # bits, so the bar for the step with the input gradient is the distance between two steps without it
+    g2, _ = step(False)
+    for a, b, c in zip(g0, g1, g2):
+        tol = max(4 * rel_err(c.cpu().numpy(), a.cpu().numpy()), 1e-6)
+        assert rel_err(b.cpu().numpy(), a.cpu().numpy()) <= tol
+    assert 'ssp_first_bwd_dgrad' not in plain
+    assert _is_subsequence(plain, with_x)
+    rest = list(with_x)
+    for n in plain:
+        rest.remove(n)
+    assert sorted(rest) == sorted(extra), rest
+    # no first-layer data gradient without the input gradient: one ssp_conv_dgrad per conv block but the first
+    nconv = sum(1 for b in model.blocks[1:] if b['type'] == 'convolutional')
+    assert plain.count('ssp_conv_dgrad') + plain.count('ssp_conv_dgrad_bnbwd') == nconv - 1
+
+
+@pytest.mark.parametrize('cfg,B,H,W', [(TINY, 2, 96, 96), (YOLO, 1, 64, 96)])
+def test_eval_mode_input_grad(cfg, B, H, W):
+    model, state = _model(cfg)
+    model.eval()
+    x = torch.from_numpy(np.random.RandomState(6).uniform(0, 1, (B, 3, H, W)).astype(np.float32))
+    xg = x.cuda().requires_grad_(True)
+    y = model(xg)
+    probe = _probe(y)
+    (y * probe.cuda()).sum().backward()
+    ref = _oracle_input_grad(model, state, x, probe, False)
+    assert rel_err(xg.grad.cpu().numpy(), ref) < TOL
+    assert all(p.grad is not None for p in model.parameters())
+
+
+@pytest.mark.parametrize('cfg,B,H,W,training', [(TINY, 2, 96, 96, True), (YOLO, 2, 64, 64, True), (TINY, 2, 64, 64, False)])
+def test_input_only_backward(monkeypatch, cfg, B, H, W, training):
+    model, state = _model(cfg)
+    model.train(training)
+    for p in model.parameters():
+        p.requires_grad_(False)
+    x = torch.from_numpy(np.random.RandomState(8).uniform(0, 1, (B, 3, H, W)).astype(np.float32))
+    for it in range(2):               # (the first backward of a plan may time kernels: record the second)
+        xg = x.cuda().requires_grad_(True)
+        y = model(xg)
+        assert y.grad_fn is not None
+        frozen = _decisions(model, B, H, W) if training else None
+        probe = _probe(y)
+        log = _record(monkeypatch) if it else []      # the backward's launches (eval mode: with its recompute forward)
+        (y * probe.cuda()).sum().backward()
+        torch.cuda.synchronize()
+    ref = _oracle_input_grad(model, state, x, probe, training, frozen)
+    assert rel_err(xg.grad.cpu().numpy(), ref) < TOL
+    assert all(p.grad is None for p in model.parameters())
+    for n in log:
+        assert not (n.startswith('ssp_conv_wgrad') or n in ('ssp_first_bwd_wgrad', 'ssp_colsum', 'ssp_sgd_step',
+                                                               'ssp_unpack_grad')), n
+    assert len(model._flat_grads) == 0
+
+
+FIRST_BODIES = {
+    'maxpool': """[maxpool]
+size=2
+stride=2
+
+[convolutional]
+batch_normalize=1
+filters=16
+size=3
+stride=1
+pad=1
+activation=leaky
+
+[convolutional]
+filters=20
+size=1
+stride=1
+pad=1
+activation=linear
+""",
+    'reorg': """[reorg]
+stride=2
+
+[convolutional]
+batch_normalize=1
+filters=16
+size=3
+stride=1
+pad=1
+activation=leaky
+
+[convolutional]
+filters=20
+size=1
+stride=1
+pad=1
+activation=linear
+"""}
+
+
+@pytest.mark.parametrize('kind', sorted(FIRST_BODIES))
+def test_first_block_not_a_conv(tmp_path, kind):
+    C = 4 if kind == 'reorg' else 3          # (ssp_reorg: channel counts that are multiples of 4)
+    model, state = _model(_cfg_with_region(tmp_path, kind + '.cfg', FIRST_BODIES[kind], C))
+    model.train()
+    x = torch.from_numpy(np.random.RandomState(9).uniform(0, 1, (2, C, 32, 48)).astype(np.float32))
+    xg = x.cuda().requires_grad_(True)
+    y = model(xg)
+    frozen = _decisions(model, 2, 32, 48)
+    probe = _probe(y)
+    (y * probe.cuda()).sum().backward()
+    from oracle.darknet_ref import forward_ref
+    with torch.no_grad():
+        y_ref = forward_ref(model.blocks, clone_state(state), x, training=True)
+    assert rel_err(y.detach().cpu().numpy(), y_ref.numpy()) < 1e-4
+    ref = _oracle_input_grad(model, state, x, probe, True, frozen)
+    assert rel_err(xg.grad.cpu().numpy(), ref) < TOL
+
+
+def test_dtypes_and_resolutions():
+    model, state = _model(TINY)
+    model.train()
+    # float64 input: float64 gradient of the same shape
+    x = torch.from_numpy(np.random.RandomState(10).uniform(0, 1, (2, 3, 64, 64)))
+    xg = x.cuda().requires_grad_(True)
+    y = model(xg)
+    probe = _probe(y)
+    (y * probe.cuda()).sum().backward()
+    assert xg.grad.dtype == torch.float64 and xg.grad.shape == xg.shape
+    assert rel_err(xg.grad.cpu().numpy(), _oracle_input_grad(model, state, x.float(), probe, True)) < TOL
+    # two resolutions on one model (two plans)
+    for H, W in ((96, 96), (128, 128)):
+        model.zero_grad(set_to_none=True)
+        x = torch.from_numpy(np.random.RandomState(H).uniform(0, 1, (2, 3, H, W)).astype(np.float32))
+        xg = x.cuda().requires_grad_(True)
+        y = model(xg)
+        probe = _probe(y)
+        (y * probe.cuda()).sum().backward()
+        assert rel_err(xg.grad.cpu().numpy(), _oracle_input_grad(model, state, x, probe, True)) < TOL
+    # uint8 input: parameter gradients as before (the float input x / 255 gives the same ones)
+    u8 = torch.from_numpy(np.random.RandomState(11).randint(0, 256, (2, 64, 64, 3)).astype(np.uint8))
+    grads = []
+    for inp in (u8.cuda(), (u8.permute(0, 3, 1, 2).float() / 255).cuda()):
+        model.zero_grad(set_to_none=True)
+        y = model(inp)
+        (y * _probe(y).cuda()).sum().backward()
+        grads.append([p.grad.detach().cpu().clone() for p in model.parameters()])
+    for a, b in zip(*grads):
+        assert torch.isfinite(a).all() and rel_err(a.numpy(), b.numpy()) < 1e-4
