@@ -1,7 +1,9 @@
 """Per-kernel parity through the C ABI (libssp_hip.so) against PyTorch-CPU fp32 references of the same op.
 
 Tolerance: SURVEY.md section 8 / BASELINE.json: bit-exact for index-only kernels (reorg, route copy, repack, max-pool
-selection), max|a-b|/max|b| <= 1e-4 for fp32 arithmetic.
+selection), max|a-b|/max|b| <= 1e-4 for fp32 arithmetic.  The bit-exact class for ARITHMETIC kernels - inputs on dyadic grids,
+every intermediate exact in fp32, leaky signs / pool winners / ties / negative scales compared with torch.equal - lives in
+tests/test_gpu_decisions.py.
 """
 import numpy as np
 import pytest
