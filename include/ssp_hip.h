@@ -247,9 +247,31 @@ typedef struct SspResampleDesc {
   int dst_w, dst_h, dst_pitch;
   int ksize, img_pitch, reserved;
 } SspResampleDesc;
-/* pass 0 = horizontal (epilogue must be 0), 1 = vertical; epilogue 0 = store, 1 = composite with img / mask,
- * 2 = distort_image (RGB -> HSV -> tables -> RGB).  max_dst_pixels = the largest dst_w * dst_h of the batch. */
+/* pass 0 = horizontal (epilogue 0 or 3), 1 = vertical (epilogue 0, 1, 2 or 4); epilogue 0 = store, 1 = composite with
+ * img / mask, 2 = distort_image (RGB -> HSV -> tables -> RGB), 3 = masked source: the taps read src * round(mask / 255)
+ * per channel, `mask` laid out as `src` (mask_background of image_multi.py; mask == NULL reads src plainly),
+ * 4 = moved destination: the result pixel (y, x) is stored at ((y + y0) % dst_h, (x + x0) % dst_w), mirrored in x
+ * when `reserved` != 0 (ImageChops.offset then FLIP_LEFT_RIGHT; 0 <= x0 < dst_w, 0 <= y0 < dst_h).
+ * max_dst_pixels = the largest dst_w * dst_h of the batch. */
 int ssp_resample_u8(const SspResampleDesc* descs_dev, int count, int pass, int epilogue, int max_dst_pixels, void* stream);
+/* The layer compositor of the multi-object augmentation (image_multi.py augment_objects + change_background): all layers
+ * are dense uint8 arrays of `nbytes` bytes (network shape x 3), 16-byte aligned.  Per byte, pos(m) = m >= 128:
+ *   total = pos(scene_mask) ? scene : 0, tmask = scene_mask;
+ *   for k < nobj: tmask = min(255, obj_mask[k] + (pos(obj_mask[k]) ? 0 : tmask)), total = pos(obj_mask[k]) ? obj[k] : total;
+ *   total = pos(scene_mask) ? scene : total;  out = pos(tmask) ? total : bg.
+ * One descriptor per sample, an array of them in DEVICE memory. */
+#define SSP_COMPOSITE_MAX_OBJS 8
+typedef struct SspCompositeDesc {
+  const void* scene;
+  const void* scene_mask;
+  const void* bg;
+  void* out;
+  const void* obj[SSP_COMPOSITE_MAX_OBJS];
+  const void* obj_mask[SSP_COMPOSITE_MAX_OBJS];
+  long long nbytes;
+  int nobj, reserved;
+} SspCompositeDesc;
+int ssp_composite_u8(const SspCompositeDesc* descs_dev, int count, long long max_bytes, void* stream);
 /* distort_image alone on npix packed RGB pixels (mode 0, lut = 768 bytes); modes 1 / 2 = RGB -> HSV / HSV -> RGB only
  * (Image.convert), which is how the tests pin both conversions over all 2^24 inputs. */
 int ssp_distort_u8(const unsigned char* rgb, unsigned char* out, int64_t npix, const unsigned char* lut, int mode, void* stream);

@@ -70,6 +70,7 @@ _SIGS = {
     "ssp_u8hwc_to_nhwc": [P, P, I, I, I, I, I, I, P],
     "ssp_resample_u8": [P, I, I, I, I, P],
     "ssp_distort_u8": [P, P, L, P, I, P],
+    "ssp_composite_u8": [P, I, L, P],
     "ssp_repack_fwd": [P, P, I, I, I, I, P],
     "ssp_repack_dgrad": [P, P, I, I, I, I, P],
     "ssp_repack_dgrad_packed": [P, P, I, I, I, I, P],

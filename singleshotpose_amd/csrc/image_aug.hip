@@ -83,7 +83,11 @@ __device__ __forceinline__ void aug_hsv2rgb(int h, int s, int v, int& r, int& g,
 }
 
 // pass 0 = horizontal (taps along x, source window + zero fill), pass 1 = vertical (taps along y, dense source).
-// epilogue 0 = store, 1 = composite (dst = mask >= 128 ? img : value, per channel), 2 = distort (HSV tables).
+// epilogue 0 = store, 1 = composite (dst = mask >= 128 ? img : value, per channel), 2 = distort (HSV tables),
+// 3 = masked source (pass 0 only: the taps read img * round(mask / 255), image_multi.py:38-50 mask_background, without
+// the masked full-size image ever being written; a descriptor without a mask reads plainly), 4 = moved destination
+// (pass 1 only: ImageChops.offset(x0, y0) with wrap-around, then FLIP_LEFT_RIGHT when `reserved` is set, as the index
+// the pixel is stored at).
 template <int PASS, int EPI>
 __global__ void __launch_bounds__(256) aug_resample_kernel(const SspResampleDesc* __restrict__ descs) {
   const SspResampleDesc d = descs[blockIdx.y];
@@ -101,7 +105,21 @@ __global__ void __launch_bounds__(256) aug_resample_kernel(const SspResampleDesc
     if (PASS == 0) {
       // logical source pixel (yo + row0, lo + x) sits at physical (y + y0, x + x0); outside the source = 0 (Image.crop)
       const int py = yo + d.row0 + d.y0;
-      if (py >= 0 && py < d.src_h) {
+      if (EPI == 3 && d.mask != nullptr) {
+        if (py >= 0 && py < d.src_h) {
+          const unsigned char* row = src + (int64_t)py * d.src_pitch;
+          const unsigned char* mrow = reinterpret_cast<const unsigned char*>(d.mask) + (int64_t)py * d.src_pitch;
+          for (int x = 0; x < n; ++x) {
+            const int px = lo + x + d.x0;
+            if (px >= 0 && px < d.src_w) {
+              const unsigned char* p = row + 3 * px;
+              const unsigned char* m = mrow + 3 * px;
+              const int c = k[x];
+              s0 += (m[0] >= 128 ? p[0] : 0) * c; s1 += (m[1] >= 128 ? p[1] : 0) * c; s2 += (m[2] >= 128 ? p[2] : 0) * c;
+            }
+          }
+        }
+      } else if (py >= 0 && py < d.src_h) {
         const unsigned char* row = src + (int64_t)py * d.src_pitch;
         for (int x = 0; x < n; ++x) {
           const int px = lo + x + d.x0;
@@ -133,9 +151,79 @@ __global__ void __launch_bounds__(256) aug_resample_kernel(const SspResampleDesc
       aug_rgb2hsv(r, g, b, h, s, v);
       aug_hsv2rgb(lut[h], lut[256 + s], lut[512 + v], r, g, b);
     }
-    unsigned char* q = dst + (int64_t)yo * d.dst_pitch + 3 * xo;
+    int ys = yo, xs = xo;
+    if (EPI == 4) {      // shifts arrive reduced to [0, size) by the launcher's caller contract (checked on the host side)
+      ys = yo + d.y0; ys = ys >= d.dst_h ? ys - d.dst_h : ys;
+      xs = xo + d.x0; xs = xs >= d.dst_w ? xs - d.dst_w : xs;
+      if (d.reserved) xs = d.dst_w - 1 - xs;
+    }
+    unsigned char* q = dst + (int64_t)ys * d.dst_pitch + 3 * xs;
     q[0] = (unsigned char)r; q[1] = (unsigned char)g; q[2] = (unsigned char)b;
   }
+}
+
+// The layer compositor of image_multi.py:299-382 (augment_objects + change_background) for one batch: every layer is a dense
+// network-shape (H, W, 3) uint8 image, so a sample is `nbytes` independent bytes and a thread owns 16 of them (one
+// 16-byte load per layer, one 16-byte store).  Per byte, with pos(m) = m >= 128 (Image.point(i / 255) rounds) and
+// neg(m) = 1 - pos(m) - the two are complementary for every byte, so every "a * pos + b * neg" of the reference is a select:
+//   total = scene * pos(scene_mask); tmask = scene_mask                      (mask_background, :316-322)
+//   per accepted object k, in order:  tmask = min(255, m_k + tmask * neg(m_k))  (superimpose_masks: int32 sum, convert('L')
+//                                     total = pos(m_k) ? obj_k : total           clips; superimpose_masked_imgs)
+//   total = pos(scene_mask) ? scene : total                                  (:363, the scene object back on top)
+//   out   = pos(tmask) ? total : bg                                          (change_background, :167-182)
+template <typename V>
+__device__ __forceinline__ void aug_composite_bytes(const SspCompositeDesc& d, int64_t off, int nb) {
+  constexpr int N = (int)sizeof(V);
+  union U { V v; unsigned char b[N]; };
+  U sc, sm, bg, tot, tm, o, m;
+  if (N > 1) {
+    sc.v = *reinterpret_cast<const V*>(reinterpret_cast<const unsigned char*>(d.scene) + off);
+    sm.v = *reinterpret_cast<const V*>(reinterpret_cast<const unsigned char*>(d.scene_mask) + off);
+    bg.v = *reinterpret_cast<const V*>(reinterpret_cast<const unsigned char*>(d.bg) + off);
+  } else {
+    sc.b[0] = reinterpret_cast<const unsigned char*>(d.scene)[off];
+    sm.b[0] = reinterpret_cast<const unsigned char*>(d.scene_mask)[off];
+    bg.b[0] = reinterpret_cast<const unsigned char*>(d.bg)[off];
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    tot.b[i] = sm.b[i] >= 128 ? sc.b[i] : 0;
+    tm.b[i] = sm.b[i];
+  }
+  for (int k = 0; k < nb; ++k) {
+    if (N > 1) {
+      o.v = *reinterpret_cast<const V*>(reinterpret_cast<const unsigned char*>(d.obj[k]) + off);
+      m.v = *reinterpret_cast<const V*>(reinterpret_cast<const unsigned char*>(d.obj_mask[k]) + off);
+    } else {
+      o.b[0] = reinterpret_cast<const unsigned char*>(d.obj[k])[off];
+      m.b[0] = reinterpret_cast<const unsigned char*>(d.obj_mask[k])[off];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const bool pos = m.b[i] >= 128;
+      const int t = (int)m.b[i] + (pos ? 0 : (int)tm.b[i]);
+      tm.b[i] = (unsigned char)(t > 255 ? 255 : t);
+      tot.b[i] = pos ? o.b[i] : tot.b[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const unsigned char t = sm.b[i] >= 128 ? sc.b[i] : tot.b[i];
+    tot.b[i] = tm.b[i] >= 128 ? t : bg.b[i];
+  }
+  if (N > 1) *reinterpret_cast<V*>(reinterpret_cast<unsigned char*>(d.out) + off) = tot.v;
+  else reinterpret_cast<unsigned char*>(d.out)[off] = tot.b[0];
+}
+
+__global__ void __launch_bounds__(256) aug_composite_kernel(const SspCompositeDesc* __restrict__ descs) {
+  const SspCompositeDesc d = descs[blockIdx.y];
+  const int nb = d.nobj;
+  const int64_t nvec = d.nbytes / 16;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+    aug_composite_bytes<uint4>(d, i * 16, nb);
+  // the tail of a layer whose size is not a multiple of 16 bytes (network shapes are multiples of 32: none)
+  for (int64_t i = nvec * 16 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < d.nbytes; i += (int64_t)gridDim.x * 256)
+    aug_composite_bytes<unsigned char>(d, i, nb);
 }
 
 // mode 0: rgb -> hsv -> tables -> rgb (distort_image); 1: rgb -> hsv only; 2: hsv -> rgb only (checkers)
@@ -157,18 +245,33 @@ __global__ void __launch_bounds__(256) aug_distort_kernel(const unsigned char* _
 int ssp_resample_u8_launch(const SspResampleDesc* descs, int count, int pass, int epilogue, int max_dst_pixels,
                            hipStream_t stream) {
   SSP_CHECK_ARG(descs != nullptr && count > 0 && max_dst_pixels > 0, "resample_u8: empty batch");
-  SSP_CHECK_ARG((pass == 0 || pass == 1) && epilogue >= 0 && epilogue <= 2 && !(pass == 0 && epilogue != 0),
-                "resample_u8: pass 0 (horizontal) stores plainly; pass 1 (vertical) takes epilogue 0 / 1 / 2");
+  SSP_CHECK_ARG((pass == 0 && (epilogue == 0 || epilogue == 3)) ||
+                    (pass == 1 && (epilogue == 0 || epilogue == 1 || epilogue == 2 || epilogue == 4)),
+                "resample_u8: pass 0 (horizontal) takes epilogue 0 / 3; pass 1 (vertical) takes epilogue 0 / 1 / 2 / 4");
   SSP_CHECK_ARG(count <= 65535, "resample_u8: at most 65535 samples per launch");
   SspProfScope prof(SSP_PROF_LAYOUT, stream, 0.0);
   int gx = (max_dst_pixels + 255) / 256;
   if (gx > 4096) gx = 4096;
   const dim3 grid(gx, count), block(256);
-  if (pass == 0) hipLaunchKernelGGL((aug_resample_kernel<0, 0>), grid, block, 0, stream, descs);
+  if (pass == 0 && epilogue == 3) hipLaunchKernelGGL((aug_resample_kernel<0, 3>), grid, block, 0, stream, descs);
+  else if (pass == 0) hipLaunchKernelGGL((aug_resample_kernel<0, 0>), grid, block, 0, stream, descs);
+  else if (epilogue == 4) hipLaunchKernelGGL((aug_resample_kernel<1, 4>), grid, block, 0, stream, descs);
   else if (epilogue == 0) hipLaunchKernelGGL((aug_resample_kernel<1, 0>), grid, block, 0, stream, descs);
   else if (epilogue == 1) hipLaunchKernelGGL((aug_resample_kernel<1, 1>), grid, block, 0, stream, descs);
   else hipLaunchKernelGGL((aug_resample_kernel<1, 2>), grid, block, 0, stream, descs);
   SSP_CHECK_LAUNCH("resample_u8");
+  return SSP_OK;
+}
+
+int ssp_composite_u8_launch(const SspCompositeDesc* descs, int count, int64_t max_bytes, hipStream_t stream) {
+  SSP_CHECK_ARG(descs != nullptr && count > 0 && max_bytes > 0, "composite_u8: empty batch");
+  SSP_CHECK_ARG(count <= 65535, "composite_u8: at most 65535 samples per launch");
+  SspProfScope prof(SSP_PROF_LAYOUT, stream, 0.0);
+  int64_t gx = (max_bytes / 16 + 255) / 256;
+  if (gx < 1) gx = 1;
+  if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(aug_composite_kernel, dim3((unsigned)gx, count), dim3(256), 0, stream, descs);
+  SSP_CHECK_LAUNCH("composite_u8");
   return SSP_OK;
 }
 
