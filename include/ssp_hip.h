@@ -336,6 +336,23 @@ int ssp_region_decode_argmax(const float* out, float* boxes, int nB, int nA, int
 int ssp_region_decode_all(const float* out, float* rows, int nB, int nA, int nC, int nH, int nW, int num_keypoints,
                           void* stream);
 
+/* Multi-object validation matching (multi_obj_pose_estimation/valid_multi.py:110-123 on top of utils_multi.py:266-382),
+ * every image on its own, one workgroup per image.  target: (nB, 50, 2K+3) floats on the device in the label layout
+ * ssp_region_loss reads; the ground-truth count of an image is the index of its first row whose column 1 is 0 (50
+ * when there is none).  For ground truth t of class c: among the cells with conf > conf_thresh (conf = det_conf *
+ * cls_max_conf, or det_conf when only_objectness) whose arg-max class is c, the one with the largest det_conf, first
+ * in scan order on a tie (source 1); when there is none, the reference's fallback box of class c - the last cell its
+ * sequential `det_conf > max_conf and p_c > max_cls_conf` walk takes (source 2); source 0 when that walk takes no cell
+ * (NaN head), when c is outside [0, nC) and for rows at or past the ground-truth count.
+ *   rows[b][t][2K+4] = {2K coords as ssp_region_decode_all, det_conf, class confidence, class, match}
+ *   meta[b][t][2]    = {source, scan-order key (cy*nW + cx)*nA + anchor, -1 when source is 0}
+ * match = corner_confidence(gt corners, predicted corners) in fp32 with th = 80, sharpness = 2, the pixel scale
+ * im_width x im_height and the exp(2) - 1 + 1e-5 normaliser.  num_keypoints == 9 only; at most 4096 cells
+ * (nA * nH * nW) per image and 65535 classes, anything larger is refused. */
+int ssp_region_match_multi(const float* out, const float* target, float* rows, int* meta, int nB, int nA, int nC, int nH,
+                           int nW, int num_keypoints, float conf_thresh, int only_objectness, int im_width, int im_height,
+                           void* stream);
+
 /* ---- PnP (utils.py:86-100: cv2.solvePnP ITERATIVE + cv2.Rodrigues) ----------------------------------------- */
 /* batched: pts3d [n][N][3], pts2d [n][N][2], K [n][9] (row-major) doubles on the device -> Rt [n][12] = R (9) | t (3) */
 int ssp_pnp_batched(const double* pts3d, const double* pts2d, const double* K, double* Rt, int n, int N, int max_iter,

@@ -354,6 +354,194 @@ __global__ void __launch_bounds__(256) region_decode_all_kernel(const float* __r
   }
 }
 
+// corner_confidence (utils_multi.py:189-210) with the caller's pixel scale: corner_conf<K> above with im_width x im_height
+// in place of 640 x 480 (the same expressions in the same order)
+template <int K>
+__device__ __forceinline__ float corner_conf_px(const float* gt, const float* pr, float conf0, float im_w, float im_h) {
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float dx = (gt[2 * k] - pr[2 * k]) * im_w;
+    float dy = (gt[2 * k + 1] - pr[2 * k + 1]) * im_h;
+    float d = sqrtf(dx * dx + dy * dy);
+    float c = (expf(2.f * (1.f - d / 80.f)) - 1.f) / conf0;
+    s += (d < 80.f) ? c : 0.f;
+  }
+  return s / (float)K;
+}
+
+// larger det first, smaller scan-order key on a tie (the first cell in scan order wins the reference's strict '>')
+__device__ __forceinline__ void match_better(float& d, int& k, float od, int ok) {
+  if (od > d || (od == d && ok < k)) { d = od; k = ok; }
+}
+
+#define SSP_MATCH_NO_KEY 0x7fffffff
+
+// Multi-object validation matching: for every ground truth (b, t) of class c the box valid_multi.py:110-123 selects
+// from get_multi_region_boxes(output[b:b+1], ..., correspondingclass = c) (utils_multi.py:266-382), each image on its
+// own.  One workgroup per image:
+//   1. every cell's det_conf, soft-max sum and arg-max class go to LDS once (region_decode_all_kernel's expressions);
+//   2. per distinct class of the image's ground truths: workgroup arg-max of det_conf over the kept cells
+//      (conf > thresh) whose arg-max class is c, first in scan order on a tie -> source 1;
+//   3. no such cell: the reference's fallback box.  It is the LAST cell taken by the sequential rule
+//      `det > max_conf and p_c > max_cls_conf` walked in scan order - no arg-max of either quantity.  Wave 0 walks the
+//      cells 64 at a time: the first lane that passes under the current (max_conf, max_cls_conf) is exactly the next
+//      cell the sequential walk takes (the lanes before it failed under thresholds that only rise), so one ballot per
+//      taken cell replays the chain exactly -> source 2; a chain that never takes a cell (NaN) -> source 0;
+//   4. one fixed row per ground-truth slot: rows[b][t] = {2K coords, det_conf, cls_conf, cls, match},
+//      meta[b][t] = {source, scan-order key}.
+template <int K>
+__global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __restrict__ out,
+                                                                 const float* __restrict__ target, int nA, int nC, int nH,
+                                                                 int nW, float conf_thresh, int only_objectness, float im_w,
+                                                                 float im_h, float* __restrict__ rows,
+                                                                 int* __restrict__ meta) {
+  constexpr int NL = 2 * K + 3;
+  constexpr int RW = 2 * K + 4;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nCh = 2 * K + 1 + nC;
+  const int64_t hw = (int64_t)nH * nW;
+  const int ncell = nA * nH * nW;
+
+  __shared__ float s_det[SSP_MAX_CELLS];             // det_conf, indexed by the scan-order key
+  __shared__ float s_se[SSP_MAX_CELLS];              // soft-max denominator: cls_max_conf = 1 / se
+  __shared__ float s_pc[SSP_MAX_CELLS];              // soft-max probability of the class whose fallback chain runs
+  __shared__ unsigned short s_cid[SSP_MAX_CELLS];    // arg-max class
+  __shared__ int gt_cls[SSP_MAX_GT], gt_first[SSP_MAX_GT];
+  __shared__ int res_src[SSP_MAX_GT], res_key[SSP_MAX_GT];
+  __shared__ float res_det[SSP_MAX_GT], res_cc[SSP_MAX_GT];
+  __shared__ float s_wd[4];
+  __shared__ int s_wk[4];
+  __shared__ int s_ngt;
+
+  const float* tg = target + (int64_t)b * SSP_MAX_GT * NL;
+  if (tid == 0) {
+    int n = 0;
+    while (n < SSP_MAX_GT && tg[n * NL + 1] != 0.f) ++n;   // valid_multi.py:20-23
+    s_ngt = n;
+  }
+  for (int key = tid; key < ncell; key += 256) {
+    int an = key % nA, rem = key / nA;
+    int64_t base = ((int64_t)(b * nA + an) * nCh) * hw + rem;
+    s_det[key] = sigmoidf_(out[base + (2 * K) * hw]);
+    float mx = -INFINITY;
+    int arg = 0;
+    for (int q = 0; q < nC; ++q) {
+      float z = out[base + (2 * K + 1 + q) * hw];
+      if (z > mx) { mx = z; arg = q; }
+    }
+    float se = 0.f;
+    for (int q = 0; q < nC; ++q) se += expf(out[base + (2 * K + 1 + q) * hw] - mx);
+    s_se[key] = se;
+    s_cid[key] = (unsigned short)arg;
+  }
+  __syncthreads();
+  const int ngt = s_ngt;
+  if (tid < SSP_MAX_GT) {
+    res_src[tid] = 0;
+    if (tid < ngt) {
+      int c = (int)tg[tid * NL];
+      int first = tid;
+      for (int u = tid - 1; u >= 0; --u)
+        if ((int)tg[u * NL] == c) first = u;
+      gt_cls[tid] = c;
+      gt_first[tid] = first;   // ground truths of one class share one result
+    }
+  }
+  __syncthreads();
+
+  for (int t = 0; t < ngt; ++t) {      // every branch below is uniform over the workgroup
+    const int c = gt_cls[t];
+    if (gt_first[t] != t || c < 0 || c >= nC) continue;
+    float bd = -INFINITY;
+    int bk = SSP_MATCH_NO_KEY;
+    for (int key = tid; key < ncell; key += 256) {
+      float d = s_det[key];
+      float conf = only_objectness ? d : d * (1.f / s_se[key]);
+      if (conf > conf_thresh && (int)s_cid[key] == c && d > bd) { bd = d; bk = key; }   // keys ascend: first maximum kept
+    }
+    for (int off = 32; off > 0; off >>= 1) match_better(bd, bk, __shfl_xor(bd, off), __shfl_xor(bk, off));
+    if (lane == 0) { s_wd[wid] = bd; s_wk[wid] = bk; }
+    __syncthreads();
+    bd = s_wd[0]; bk = s_wk[0];
+    for (int w = 1; w < 4; ++w) match_better(bd, bk, s_wd[w], s_wk[w]);
+    if (bk != SSP_MATCH_NO_KEY) {
+      if (tid == 0) { res_src[t] = 1; res_key[t] = bk; res_det[t] = s_det[bk]; res_cc[t] = 1.f / s_se[bk]; }
+    } else {
+      for (int key = tid; key < ncell; key += 256) {
+        int an = key % nA, rem = key / nA;
+        int64_t base = ((int64_t)(b * nA + an) * nCh) * hw + rem;
+        float mx = -INFINITY;
+        for (int q = 0; q < nC; ++q) {
+          float z = out[base + (2 * K + 1 + q) * hw];
+          if (z > mx) mx = z;
+        }
+        s_pc[key] = expf(out[base + (2 * K + 1 + c) * hw] - mx) / s_se[key];
+      }
+      __syncthreads();
+      if (wid == 0) {
+        float m = -1.f, q = -9223372036854775807.f;   // max_conf = -1, max_cls_conf = -sys.maxsize
+        int taken = -1;
+        for (int base = 0; base < ncell; base += 64) {
+          const int key = base + lane;
+          const bool valid = key < ncell;
+          const float d = valid ? s_det[key] : 0.f, p = valid ? s_pc[key] : 0.f;
+          while (true) {
+            const unsigned long long pass = __ballot(valid && d > m && p > q);
+            if (pass == 0ull) break;
+            const int f = __ffsll((long long)pass) - 1;
+            m = __shfl(d, f); q = __shfl(p, f);
+            taken = base + f;
+          }
+        }
+        if (lane == 0 && taken >= 0) { res_src[t] = 2; res_key[t] = taken; res_det[t] = m; res_cc[t] = q; }
+      }
+    }
+    __syncthreads();   // s_wd / s_pc are reused by the next class; res_* is read below
+  }
+
+  if (tid < SSP_MAX_GT) {
+    const int t = tid;
+    float* o = rows + ((int64_t)b * SSP_MAX_GT + t) * RW;
+    int* mo = meta + ((int64_t)b * SSP_MAX_GT + t) * 2;
+    int src = 0, r = 0;
+    if (t < ngt && gt_cls[t] >= 0 && gt_cls[t] < nC) { r = gt_first[t]; src = res_src[r]; }
+    if (src == 0) {
+#pragma unroll
+      for (int k = 0; k < RW; ++k) o[k] = 0.f;
+      mo[0] = 0; mo[1] = -1;
+    } else {
+      const int key = res_key[r];
+      const int an = key % nA, rem = key / nA;
+      const int j = rem / nW, i = rem % nW;
+      float pr[2 * K], gc[2 * K];
+      decode_cell<K>(out, ((int64_t)(b * nA + an) * nCh) * hw + rem, hw, i, j, nW, nH, pr);
+#pragma unroll
+      for (int k = 0; k < 2 * K; ++k) { gc[k] = tg[t * NL + 1 + k]; o[k] = pr[k]; }
+      o[2 * K] = res_det[r];
+      o[2 * K + 1] = res_cc[r];
+      o[2 * K + 2] = (float)gt_cls[t];
+      o[2 * K + 3] = corner_conf_px<K>(gc, pr, expf(2.f) - 1.f + 1e-5f, im_w, im_h);
+      mo[0] = src; mo[1] = key;
+    }
+  }
+}
+
+int ssp_region_match_multi_launch(const float* out, const float* target, float* rows, int* meta, int nB, int nA, int nC,
+                                  int nH, int nW, int num_keypoints, float conf_thresh, int only_objectness, int im_width,
+                                  int im_height, hipStream_t stream) {
+  SSP_CHECK_ARG(num_keypoints == 9, "region_match_multi: only num_keypoints == 9 is built (got %d)", num_keypoints);
+  SSP_CHECK_ARG(out && target && rows && meta, "region_match_multi: null buffer");
+  SSP_CHECK_ARG(nB >= 1 && nA >= 1 && nH >= 1 && nW >= 1, "region_match_multi: empty head");
+  SSP_CHECK_ARG(nC >= 1 && nC <= 65535, "region_match_multi: need 1..65535 classes (got %d)", nC);
+  SSP_CHECK_ARG((int64_t)nA * nH * nW <= SSP_MAX_CELLS, "region_match_multi: more than %d cells per image", SSP_MAX_CELLS);
+  SspProfScope prof(SSP_PROF_REGION, stream, 0.0);
+  hipLaunchKernelGGL((region_match_multi_kernel<9>), dim3(nB), dim3(256), 0, stream, out, target, nA, nC, nH, nW,
+                     conf_thresh, only_objectness, (float)im_width, (float)im_height, rows, meta);
+  SSP_CHECK_LAUNCH("region_match_multi");
+  return SSP_OK;
+}
+
 int ssp_region_decode_all_launch(const float* out, float* rows, int nB, int nA, int nC, int nH, int nW,
                                  int num_keypoints, hipStream_t stream) {
   SSP_CHECK_ARG(num_keypoints == 9, "region_decode_all: only num_keypoints == 9 is built (got %d)", num_keypoints);

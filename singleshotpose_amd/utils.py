@@ -108,12 +108,20 @@ def pnp_batched(points_3D, points_2D, cameraMatrix, max_iter=20):
     if not torch.cuda.is_available():
         raise RuntimeError("pnp runs on the MI355X HIP kernel only (no CPU fallback; cv2 is not used)")
     dev = torch.device('cuda', torch.cuda.current_device())
-    p3, p2, Kt = p3.to(dev), p2.to(dev), Kt.to(dev)
-    Rt = torch.empty(n, 12, dtype=torch.float64, device=dev)
+    Rt = pnp_device(p3.to(dev), p2.to(dev), Kt.to(dev), max_iter).cpu().numpy()
+    return Rt[:, :9].reshape(n, 3, 3).copy(), Rt[:, 9:].reshape(n, 3, 1).copy()
+
+
+def pnp_device(p3, p2, Kt, max_iter=20):
+    """pnp_batched's launch on tensors that already live on the device, nothing returned to the host: contiguous
+    float64 p3 (n,N,3), p2 (n,N,2), Kt (n,3,3) -> (n,12) float64 device tensor, R (9, row-major) | t (3) per problem."""
+    n, N = p3.size(0), p3.size(1)
+    for t, tail in ((p3, (N, 3)), (p2, (N, 2)), (Kt, (3, 3))):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (n,) + tail
+    Rt = torch.empty(n, 12, dtype=torch.float64, device=p3.device)
     _lib.call('ssp_pnp_batched', p3.data_ptr(), p2.data_ptr(), Kt.data_ptr(), Rt.data_ptr(), n, N, max_iter,
               torch.cuda.current_stream().cuda_stream)
-    Rt = Rt.cpu().numpy()
-    return Rt[:, :9].reshape(n, 3, 3).copy(), Rt[:, 9:].reshape(n, 3, 1).copy()
+    return Rt
 
 
 def _to_dev_f64(a):
@@ -144,10 +152,20 @@ def pose_errors_batched(vertices, R_gt, t_gt, R_pr, t_pr, internal_calibration):
         raise ValueError("internal_calibration must be (3,3) or (n,3,3)")
     Rt_gt = torch.cat((Rg, tg), dim=1).contiguous()
     Rt_pr = torch.cat((Rp, tp), dim=1).contiguous()
+    return pose_errors_device(v, Rt_gt, Rt_pr, K).cpu().numpy()
+
+
+def pose_errors_device(v, Rt_gt, Rt_pr, K):
+    """pose_errors_batched's launch on tensors that already live on the device, nothing returned to the host:
+    contiguous float64 v (N,3), Rt_gt / Rt_pr (n,12) in pnp_device's layout, K (1,9) or (n,9) -> (n,4) device tensor."""
+    n = Rt_gt.size(0)
+    for t, shape in ((v, (v.size(0), 3)), (Rt_gt, (n, 12)), (Rt_pr, (n, 12)), (K, (K.size(0), 9))):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+    assert K.size(0) in (1, n)
     out = torch.empty(n, 4, dtype=torch.float64, device=v.device)
     _lib.call('ssp_pose_errors', v.data_ptr(), v.size(0), Rt_gt.data_ptr(), Rt_pr.data_ptr(), K.data_ptr(),
               1 if (K.size(0) == n and n > 1) else 0, n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    return out.cpu().numpy()
+    return out
 
 
 def calc_pts_diameter_gpu(pts):

@@ -6,7 +6,12 @@ because the reference's scripts do `from utils_multi import *`).  The per-cell d
 variable-length box lists are assembled on the host from that one device->host copy, with the reference's rules:
 threshold on det_conf (only_objectness) or det_conf*cls_max_conf; a fallback box of `correspondingclass` when no kept
 box has that class; `max_cls_conf` is NOT reset per image.
+
+match_multi_region_boxes / evaluate_multi_batched are the batched validator (valid_multi.py:94-149 for every image and
+every ground truth of a batch, all object classes in one pass): ssp_region_match_multi selects the box of each ground
+truth on the device, one fused ssp_pnp_batched launch and one ssp_pose_errors launch follow, one copy returns the result.
 """
+import collections
 import sys
 
 import numpy as np
@@ -14,6 +19,9 @@ import torch
 
 from . import _lib
 from .utils import *  # noqa: F401,F403
+from .utils import _to_dev_f64, get_3D_corners, pnp_device, pose_errors_device
+
+MAX_GT = 50      # label rows per image (dataset_multi.py pads every label file to 50 rows)
 
 
 def _span(lo_a, hi_a, lo_b, hi_b):
@@ -107,3 +115,117 @@ def get_multi_region_boxes(output, conf_thresh, num_classes, num_keypoints, anch
                          [float(max_conf), float(max_cls_conf), correspondingclass])
         all_boxes.append(boxes)
     return all_boxes
+
+
+MultiMatch = collections.namedtuple('MultiMatch', 'boxes source key match')
+MultiEval = collections.namedtuple('MultiEval', 'image gt cls source corners2D_pr match R_gt t_gt R_pr t_pr errors')
+
+
+def _head_f32(output, num_classes, num_keypoints, num_anchors, who):
+    if output.dim() == 3:
+        output = output.unsqueeze(0)
+    if not output.is_cuda:
+        raise RuntimeError("%s runs on the MI355X HIP kernel only: got a %s tensor (no CPU fallback)" % (who, output.device))
+    assert output.size(1) == (2 * num_keypoints + 1 + num_classes) * num_anchors
+    return output.detach().to(torch.float32).contiguous()
+
+
+def _labels(target, B, num_keypoints):
+    """The DataLoader's (B, 50*(2K+3)) label tensor (host or device, any float type) as (B, 50, 2K+3), not yet moved."""
+    t = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+    return t.detach().reshape(B, MAX_GT, 2 * num_keypoints + 3)
+
+
+def match_multi_region_boxes(output, target, conf_thresh, num_classes, num_keypoints, num_anchors, only_objectness=0,
+                             im_width=640, im_height=480):
+    """The box valid_multi.py:110-123 selects for every ground truth of every image, in one launch (no host loop).
+
+    output: the raw head (B, nA*(2K+1+nC), H, W) on the device; target: the (B, 50*(2K+3)) labels, host or device.
+    For ground truth k of image b, of class c, the result is what get_multi_region_boxes(output[b:b+1], ...,
+    correspondingclass=c, only_objectness) followed by the validator's best-det_conf selection yields.  Returns device
+    tensors, one fixed row per label slot:
+      boxes  (B, 50, 2K+3) float32  2K normalised corner coordinates, det_conf, class confidence, class
+      source (B, 50) int32          1 a kept cell of class c, 2 the fallback box, 0 no result: a row at or past the
+                                    image's ground-truth count, a class outside [0, nC), or a head whose det_conf is NaN
+                                    everywhere (the reference raises UnboundLocalError there); such rows are all zero
+      key    (B, 50) int32          scan-order index (cy*W + cx)*nA + anchor of the selected cell, -1 when source is 0
+      match  (B, 50) float32        corner_confidence(ground-truth corners, predicted corners) at im_width x im_height
+
+    IMAGES ARE INDEPENDENT.  The reference carries max_cls_conf and max_ind from one image of a batched call over to the
+    next (get_multi_region_boxes above reproduces that), but it only ever calls the function at batch 1; this function
+    gives every image the batch-1 result.
+    """
+    K = num_keypoints
+    out = _head_f32(output, num_classes, K, num_anchors, "match_multi_region_boxes")
+    B, h, w = out.size(0), out.size(2), out.size(3)
+    tgt = _labels(target, B, K).to(device=out.device, dtype=torch.float32).contiguous()
+    rows = torch.empty(B, MAX_GT, 2 * K + 4, dtype=torch.float32, device=out.device)
+    meta = torch.empty(B, MAX_GT, 2, dtype=torch.int32, device=out.device)
+    _lib.call('ssp_region_match_multi', out.data_ptr(), tgt.data_ptr(), rows.data_ptr(), meta.data_ptr(), B, num_anchors,
+              num_classes, h, w, K, float(conf_thresh), 1 if only_objectness else 0, int(im_width), int(im_height),
+              torch.cuda.current_stream().cuda_stream)
+    return MultiMatch(rows[..., :2 * K + 3], meta[..., 0], meta[..., 1], rows[..., 2 * K + 3])
+
+
+def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoints, anchors, num_anchors, vertices,
+                           intrinsic_calibration, im_width, im_height, only_objectness=0):
+    """valid_multi.py:94-149 for all images and all ground truths of a batch, every object class in the same pass.
+
+    match_multi_region_boxes, then on the device: both corner sets denormalised in float32, fix_corner_order on the
+    ground-truth corners, ONE PnP launch over the 2n problems (ground truths first, predictions after) with the object
+    points (centroid 0 + the 8 corners of get_3D_corners(vertices)) and K rounded to float32 as valid_multi.py:135-136
+    does, one pose-error launch with the float64 K, one device->host copy.  Which label rows are ground truths (row
+    index below the image's count, class inside [0, nC)) is read from the labels on the host - free for the host tensor
+    a DataLoader yields; a device `target` costs one extra copy of its first two columns.  Rows the kernel reports as
+    source 0 (NaN head) are dropped.  Images are independent (see match_multi_region_boxes).
+
+    Returns numpy arrays over the n surviving ground truths, in (image, row) order: image, gt (label row), cls, source
+    (n,) ints; corners2D_pr (n,9,2) float32 pixels; match (n,) float32; R_gt, R_pr (n,3,3), t_gt, t_pr (n,3,1) float64;
+    errors (n,4) float64 in pose_errors_batched's column order."""
+    K = num_keypoints
+    out = _head_f32(output, num_classes, K, num_anchors, "evaluate_multi_batched")
+    dev = out.device
+    lab = _labels(target, out.size(0), K)
+    m = match_multi_region_boxes(out, lab, conf_thresh, num_classes, K, num_anchors, only_objectness, im_width, im_height)
+    head = lab[..., :2].to(torch.float32).cpu().numpy()
+    image, gt = [], []
+    for b in range(head.shape[0]):
+        stop = np.nonzero(head[b, :, 1] == 0)[0]
+        for k in range(int(stop[0]) if len(stop) else MAX_GT):
+            if np.isfinite(head[b, k, 0]) and 0 <= int(head[b, k, 0]) < num_classes:
+                image.append(b)
+                gt.append(k)
+    image, gt = np.asarray(image, dtype=np.int64), np.asarray(gt, dtype=np.int64)
+    n = len(image)
+    cls = head[image, gt, 0].astype(np.int64) if n else np.zeros(0, dtype=np.int64)
+    if n == 0:
+        z = np.zeros
+        return MultiEval(image, gt, cls, z(0, dtype=np.int64), z((0, K, 2), dtype=np.float32), z(0, dtype=np.float32),
+                         z((0, 3, 3)), z((0, 3, 1)), z((0, 3, 3)), z((0, 3, 1)), z((0, 4)))
+    bi, ki = torch.as_tensor(image).to(dev), torch.as_tensor(gt).to(dev)
+    scale = torch.tensor([float(im_width), float(im_height)], dtype=torch.float32, device=dev)
+    order = torch.tensor([0, 1, 3, 5, 7, 2, 4, 6, 8], device=dev)                      # fix_corner_order
+    tgt = lab.to(device=dev, dtype=torch.float32)
+    c_gt = (tgt[bi, ki, 1:2 * K + 1].reshape(n, K, 2) * scale)[:, order]
+    c_pr = m.boxes[bi, ki, :2 * K].reshape(n, K, 2) * scale
+    corners3D = get_3D_corners(np.asarray(vertices.cpu() if torch.is_tensor(vertices) else vertices))
+    obj = np.array(np.transpose(np.concatenate((np.zeros((3, 1)), corners3D[:3, :]), axis=1)), dtype='float32')
+    K32 = np.array(np.asarray(intrinsic_calibration.cpu() if torch.is_tensor(intrinsic_calibration)
+                              else intrinsic_calibration), dtype='float32')
+    p3 = torch.as_tensor(obj.astype(np.float64)).to(dev).expand(2 * n, K, 3).contiguous()
+    Kt = torch.as_tensor(K32.astype(np.float64)).to(dev).expand(2 * n, 3, 3).contiguous()
+    Rt = pnp_device(p3, torch.cat((c_gt, c_pr), dim=0).to(torch.float64).contiguous(), Kt)
+    v = _to_dev_f64(vertices)
+    if v.dim() != 2 or v.size(0) not in (3, 4):
+        raise ValueError("vertices must be (3,N) or (4,N)")
+    err = pose_errors_device(v[:3].t().contiguous(), Rt[:n], Rt[n:], _to_dev_f64(intrinsic_calibration).reshape(1, 9))
+    packed = torch.cat((m.source[bi, ki].to(torch.float64).unsqueeze(1), m.match[bi, ki].to(torch.float64).unsqueeze(1),
+                        c_pr.reshape(n, 2 * K).to(torch.float64), Rt[:n], Rt[n:], err), dim=1).cpu().numpy()
+    keep = packed[:, 0] != 0
+    packed = packed[keep]
+    o = 2 + 2 * K
+    return MultiEval(image[keep], gt[keep], cls[keep], packed[:, 0].astype(np.int64),
+                     packed[:, 2:o].astype(np.float32).reshape(-1, K, 2), packed[:, 1].astype(np.float32),
+                     packed[:, o:o + 9].reshape(-1, 3, 3).copy(), packed[:, o + 9:o + 12].reshape(-1, 3, 1).copy(),
+                     packed[:, o + 12:o + 21].reshape(-1, 3, 3).copy(), packed[:, o + 21:o + 24].reshape(-1, 3, 1).copy(),
+                     packed[:, o + 24:o + 28].copy())

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Latency-bound pieces of the path (SURVEY.md section 8(d) config 4 and the 'report us per call' rows): eval-mode
-forward at 672x672 (valid.py's test size), decode, batched PnP, batched pose errors, RegionLoss, fused SGD.
-Prints one JSON object; numbers go to DESIGN.md section 3."""
+forward at 672x672 (valid.py's test size), decode, batched PnP, batched pose errors, RegionLoss, fused SGD, and the
+multi-object validator (eval_multi: evaluate_multi_batched against today's per-ground-truth host route).
+Prints one JSON object; numbers go to DESIGN.md section 3.  `infer_bench.py eval_multi` runs that line alone."""
 import json
 import os
 import sys
@@ -25,7 +26,63 @@ def timed(fn, iters, warm=3):
     return (time.perf_counter() - t0) / iters
 
 
+def eval_multi(res):
+    """B=64, 5x13x13 head, 13 classes, 2 ground truths per image.  `batched`: one evaluate_multi_batched call (match
+    kernel, one fused PnP launch, one pose-error launch, one copy).  `per_gt_host_route`: what a validator can do without
+    it - per ground truth a batch-1 get_multi_region_boxes for its class, the selection loop of valid_multi.py:118-123 and
+    two pnp calls (its pose errors are NOT included, the batched call's are)."""
+    from singleshotpose_amd import utils_multi as UM
+    B, nA, nC, K, grid, thresh = 64, 5, 13, 9, 13, 0.05
+    anchors = [1.4820, 2.2412, 2.0501, 3.1265, 2.3946, 4.6891, 3.1018, 3.9910, 3.4879, 5.8851]
+    g = torch.Generator().manual_seed(0)
+    head = torch.randn(B, nA, 2 * K + 1 + nC, grid, grid, generator=g)
+    head[:, :, 2 * K] -= 3.0                              # a few dozen cells per image above the threshold
+    head = head.view(B, -1, grid, grid).cuda()
+    rs = np.random.RandomState(0)
+    tgt = np.zeros((B, 50, 2 * K + 3), dtype=np.float32)
+    for b in range(B):
+        for k in range(2):
+            c = rs.uniform(0.3, 0.7, 2)
+            tgt[b, k, 0] = rs.randint(0, nC)
+            tgt[b, k, 1:2 * K + 1] = (c[None, :] + rs.uniform(-0.1, 0.1, (K, 2))).reshape(-1)
+    target = torch.from_numpy(tgt.reshape(B, -1))
+    half = np.array([0.038, 0.039, 0.046])
+    verts = np.concatenate(((rs.uniform(-1, 1, (5841, 3)) * half).T, np.ones((1, 5841))), axis=0)
+    Kc = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.5704, 242.0489], [0.0, 0.0, 1.0]])
+    obj = np.array(np.concatenate((np.zeros((3, 1)), UM.get_3D_corners(verts)[:3, :]), axis=1).T, dtype='float32')
+    K32 = np.array(Kc, dtype='float32')
+
+    def batched():
+        return UM.evaluate_multi_batched(head, target, thresh, nC, K, anchors, nA, verts, Kc, 640, 480)
+
+    def per_gt():
+        poses = 0
+        for b in range(B):
+            for k in range(2):
+                c = int(tgt[b, k, 0])
+                boxes = UM.get_multi_region_boxes(head[b:b + 1], thresh, nC, K, anchors, nA, c, only_objectness=0)[0]
+                best = -sys.maxsize
+                for bx in boxes:
+                    if bx[2 * K] > best and bx[2 * K + 2] == c:
+                        best, box_pr = bx[2 * K], bx
+                gt = np.array(np.reshape(tgt[b, k, 1:2 * K + 1], [-1, 2]), dtype='float32') * np.float32([640, 480])
+                pr = np.array(np.reshape(box_pr[:2 * K], [-1, 2]), dtype='float32') * np.float32([640, 480])
+                UM.pnp(obj, UM.fix_corner_order(gt), K32)
+                UM.pnp(obj, pr, K32)
+                poses += 1
+        return poses
+
+    n = len(batched().image)
+    res['eval_multi_b64_13x13_2gt_batched'] = {'us': round(timed(batched, 20) * 1e6, 1), 'ground_truths': n}
+    res['eval_multi_b64_13x13_2gt_per_gt_host_route'] = {'us': round(timed(per_gt, 2, warm=1) * 1e6, 1), 'ground_truths': per_gt()}
+
+
 def main():
+    if sys.argv[1:] == ['eval_multi']:
+        res = {}
+        eval_multi(res)
+        print(json.dumps(res))
+        return
     from singleshotpose_amd import utils as U
     from singleshotpose_amd.darknet import Darknet
     from singleshotpose_amd.region_loss import RegionLoss
@@ -78,6 +135,7 @@ def main():
     res['region_loss_fwd_b64_device_labels'] = {'us': round(dt * 1e6, 1)}
     dt = timed(lambda: crit(head, tgt, 20), 50)
     res['region_loss_fwd_b64_host_f64_labels'] = {'us': round(dt * 1e6, 1)}
+    eval_multi(res)
     print(json.dumps(res))
 
 
