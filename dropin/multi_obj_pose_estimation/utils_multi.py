@@ -1,4 +1,4 @@
 """Drop-in for multi_obj_pose_estimation/utils_multi.py (`from utils_multi import *`)."""
 from singleshotpose_amd.utils_multi import *  # noqa: F401,F403
 from singleshotpose_amd.utils_multi import (bbox_iou, evaluate_multi_batched, get_multi_region_boxes,  # noqa: F401
-                                            match_multi_region_boxes, nms)
+                                            match_multi_region_boxes, nms, summarize_multi)

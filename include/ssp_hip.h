@@ -367,6 +367,30 @@ int ssp_pose_errors(const double* vertices, int N, const double* Rt_gt, const do
                     int k_per_pose, int n, double* out, void* stream);
 /* calc_pts_diameter (utils.py:50-58): out[0] = largest pairwise distance of pts [N][3]; scratch: 8 bytes */
 int ssp_pts_diameter(const double* pts, int N, double* out, double* scratch, void* stream);
+/* The same four numbers with one mesh PER POSE (multi_obj_pose_estimation/valid_multi.py:47-50 loads a mesh per object;
+ * valid.py:146-172 is the maths): verts [sumN][3] holds the nM meshes back to back, model_off [nM+1] int32 their vertex
+ * offsets (model m is verts[model_off[m] .. model_off[m+1])), pose_model [n] int32 the mesh of each pose.  Pose i
+ * averages over the vertices of its own mesh and divides by that mesh's count; with one mesh the result has the bits
+ * of the single-mesh entry point above (one loop body serves both kernels).  THE CALLER GUARANTEES: model_off
+ * non-decreasing with every model non-empty, pose_model values in [0, nM) - the kernel does not re-check them (the
+ * Python layer validates them before the launch).  nM <= 0 is refused. */
+int ssp_pose_errors_models(const double* verts, const int* model_off, const int* pose_model, int nM, const double* Rt_gt,
+                           const double* Rt_pr, const double* K, int k_per_pose, int n, double* out, void* stream);
+/* ADD-S, the metric of symmetric objects: adi(pts_est, pts_gt) of utils.py:60-63 /
+ * multi_obj_pose_estimation/utils_multi.py:66-69, where the KD-tree is built on the ESTIMATED points and queried with
+ * the GROUND-TRUTH points:
+ *   out[i] = mean over g of  min over e of  || (R_gt v_g + t_gt) - (R_pr v_e + t_pr) ||,   g, e over the mesh of pose i
+ * (the other direction is another number).  Brute force over all pairs in fp64: every squared distance is
+ * (dx*dx + dy*dy) + dz*dz, each product and sum rounded on its own, one square root per query after the sweep; the
+ * partial sums of a pose are added in a fixed order (no floating-point atomics), so two launches give the same bits.
+ * verts / model_off / pose_model / Rt_* as for the per-mesh pose errors, with the same guarantees by the caller;
+ * maxN >= the vertex count of every mesh a pose refers to (it sizes the grid; vertices past it would be left out, never
+ * read out of range).  workspace: at least workspace_doubles(n, maxN) doubles on the device, refused when
+ * `workspace_doubles` says it is smaller. */
+int64_t ssp_adds_workspace_doubles(int n, int maxN);
+int ssp_adds_errors(const double* verts, const int* model_off, const int* pose_model, int nM, int maxN,
+                    const double* Rt_gt, const double* Rt_pr, int n, double* out, double* workspace,
+                    int64_t workspace_doubles, void* stream);
 
 /* ---- timed-launch bookkeeping (bench.py roofline): HIP events around every launch of a kernel family -------- */
 /* mask: bit k = kernel family k (0 conv fwd, 1 conv dgrad, 2 conv wgrad, 3 BN/activation, 4 layout, 5 region/pnp/eval,

@@ -64,6 +64,9 @@ _SIGS = {
     "ssp_colsum": [P, I, L, I, P, P],
     "ssp_pose_errors": [P, I, P, P, P, I, I, P, P],
     "ssp_pts_diameter": [P, I, P, P, P],
+    "ssp_pose_errors_models": [P, P, P, I, P, P, P, I, I, P, P],
+    "ssp_adds_workspace_doubles": [I, I],
+    "ssp_adds_errors": [P, P, P, I, I, P, P, I, P, P, L, P],
     "ssp_sgd_step": [P, P, P, L, F, F, F, F, I, I, P],
     "ssp_nchw_to_nhwc": [P, P, I, I, I, I, I, I, P],
     "ssp_nhwc_to_nchw": [P, P, I, I, I, I, I, P],
@@ -98,7 +101,7 @@ _SIGS = {
 }
 
 _RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',
-          'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_first_wgrad_workspace_floats')
+          'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles')
 
 PROF_KINDS = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_act", "layout", "region", "optim", "first_block_fwd",
               "first_block_bwd", "wino_fwd", "wino_dgrad", "wino_wgrad", "onchip_fwd", "onchip_dgrad", "onchip_wgrad")

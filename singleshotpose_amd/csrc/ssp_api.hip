@@ -65,6 +65,13 @@ int ssp_nhwc_to_nchw_launch(const float* src, float* dst, int B, int C, int H, i
 int ssp_pose_errors_launch(const double* verts, int N, const double* Rt_gt, const double* Rt_pr, const double* K,
                            int k_per_pose, int n, double* out, hipStream_t stream);
 int ssp_pts_diameter_launch(const double* pts, int N, double* out, double* scratch, hipStream_t stream);
+int ssp_pose_errors_models_launch(const double* verts, const int* model_off, const int* pose_model, int nM,
+                                  const double* Rt_gt, const double* Rt_pr, const double* K, int k_per_pose, int n,
+                                  double* out, hipStream_t stream);
+int64_t ssp_adds_workspace_doubles_impl(int n, int maxN);
+int ssp_adds_errors_launch(const double* verts, const int* model_off, const int* pose_model, int nM, int maxN,
+                           const double* Rt_gt, const double* Rt_pr, int n, double* out, double* workspace,
+                           int64_t workspace_doubles, hipStream_t stream);
 int ssp_resample_u8_launch(const SspResampleDesc* descs, int count, int pass, int epilogue, int max_dst_pixels, hipStream_t stream);
 int ssp_distort_u8_launch(const unsigned char* rgb, unsigned char* out, int64_t npix, const unsigned char* lut, int mode, hipStream_t stream);
 int ssp_composite_u8_launch(const SspCompositeDesc* descs, int count, int64_t max_bytes, hipStream_t stream);
@@ -474,6 +481,18 @@ int ssp_pose_errors(const double* vertices, int N, const double* Rt_gt, const do
 }
 int ssp_pts_diameter(const double* pts, int N, double* out, double* scratch, void* stream) {
   return ssp_pts_diameter_launch(pts, N, out, scratch, (hipStream_t)stream);
+}
+int ssp_pose_errors_models(const double* verts, const int* model_off, const int* pose_model, int nM, const double* Rt_gt,
+                           const double* Rt_pr, const double* K, int k_per_pose, int n, double* out, void* stream) {
+  return ssp_pose_errors_models_launch(verts, model_off, pose_model, nM, Rt_gt, Rt_pr, K, k_per_pose, n, out,
+                                       (hipStream_t)stream);
+}
+int64_t ssp_adds_workspace_doubles(int n, int maxN) { return ssp_adds_workspace_doubles_impl(n, maxN); }
+int ssp_adds_errors(const double* verts, const int* model_off, const int* pose_model, int nM, int maxN,
+                    const double* Rt_gt, const double* Rt_pr, int n, double* out, double* workspace,
+                    int64_t workspace_doubles, void* stream) {
+  return ssp_adds_errors_launch(verts, model_off, pose_model, nM, maxN, Rt_gt, Rt_pr, n, out, workspace, workspace_doubles,
+                                (hipStream_t)stream);
 }
 int ssp_prof_nkinds(void) { return SSP_PROF_NKINDS; }
 int ssp_prof_collect(double* ms, double* work, int64_t* count) {

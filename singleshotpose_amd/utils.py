@@ -168,6 +168,130 @@ def pose_errors_device(v, Rt_gt, Rt_pr, K):
     return out
 
 
+def _pack_models(models):
+    """[(3|4, N) arrays] -> (concatenated (sumN,3) float64 ndarray, (nM+1,) int32 offsets), on the host; ValueError for
+    an empty list or a mesh of another shape (nothing has touched the GPU yet)."""
+    models = list(models)
+    if len(models) == 0:
+        raise ValueError("no object model given")
+    rows = []
+    for v in models:
+        v = np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64)
+        if v.ndim != 2 or v.shape[0] not in (3, 4) or v.shape[1] == 0:
+            raise ValueError("every object model must be (3,N) or (4,N) with N > 0, got %s" % (v.shape,))
+        rows.append(v[:3].T)
+    off = np.zeros(len(rows) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    return np.ascontiguousarray(np.concatenate(rows, axis=0)), off
+
+
+def _pack_poses(R_gt, t_gt, R_pr, t_pr):
+    """Host (n,12) float64 R | t blocks of both pose sets; ValueError when the four counts differ."""
+    host = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.float64)
+    Rg, Rp = host(R_gt).reshape(-1, 9), host(R_pr).reshape(-1, 9)
+    tg, tp = host(t_gt).reshape(-1, 3), host(t_pr).reshape(-1, 3)
+    if not (len(Rg) == len(Rp) == len(tg) == len(tp)):
+        raise ValueError("R_gt, t_gt, R_pr, t_pr must hold the same number of poses")
+    return np.concatenate((Rg, tg), axis=1), np.concatenate((Rp, tp), axis=1)
+
+
+def pose_errors_models_device(v, model_off, pose_model, Rt_gt, Rt_pr, K):
+    """pose_errors_device with one mesh per pose (ssp_pose_errors_models), nothing returned to the host: v (sumN,3)
+    float64 holds the meshes back to back, model_off (nM+1,) int32 their vertex offsets (non-decreasing, no empty mesh),
+    pose_model (n,) int32 in [0, nM) - the caller has validated the last two, the kernel does not -> (n,4)."""
+    n = Rt_gt.size(0)
+    for t, shape in ((v, (v.size(0), 3)), (Rt_gt, (n, 12)), (Rt_pr, (n, 12)), (K, (K.size(0), 9))):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+    for t, shape in ((model_off, (model_off.size(0),)), (pose_model, (n,))):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape
+    assert K.size(0) in (1, n) and model_off.size(0) >= 2
+    out = torch.empty(n, 4, dtype=torch.float64, device=v.device)
+    _lib.call('ssp_pose_errors_models', v.data_ptr(), model_off.data_ptr(), pose_model.data_ptr(), model_off.size(0) - 1,
+              Rt_gt.data_ptr(), Rt_pr.data_ptr(), K.data_ptr(), 1 if (K.size(0) == n and n > 1) else 0, n, out.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def adds_device(v, model_off, pose_model, Rt_pr, Rt_gt, max_vertices=None):
+    """ADD-S of n pose pairs on tensors that already live on the device, nothing returned to the host (ssp_adds_errors):
+    per pose the mean, over the ground-truth-posed vertices of its mesh, of the distance to the NEAREST predicted-posed
+    vertex - adi(pts_est, pts_gt) of the reference (utils.py:60-63), estimate first.  v / model_off / pose_model as in
+    pose_errors_models_device (same guarantees by the caller), Rt_pr / Rt_gt (n,12) in pnp_device's layout -> (n,) float64
+    device tensor.  max_vertices: the largest vertex count among the meshes (it sizes the grid); when it is not given it
+    is read from model_off, which costs one small copy to the host."""
+    n = Rt_gt.size(0)
+    for t, shape in ((v, (v.size(0), 3)), (Rt_gt, (n, 12)), (Rt_pr, (n, 12))):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+    for t, shape in ((model_off, (model_off.size(0),)), (pose_model, (n,))):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape
+    assert model_off.size(0) >= 2
+    if max_vertices is None:
+        max_vertices = int((model_off[1:] - model_off[:-1]).max().item())
+    words = _lib.query('ssp_adds_workspace_doubles', n, int(max_vertices))
+    work = torch.empty(max(int(words), 1), dtype=torch.float64, device=v.device)
+    out = torch.empty(n, dtype=torch.float64, device=v.device)
+    _lib.call('ssp_adds_errors', v.data_ptr(), model_off.data_ptr(), pose_model.data_ptr(), model_off.size(0) - 1,
+              int(max_vertices), Rt_gt.data_ptr(), Rt_pr.data_ptr(), n, out.data_ptr(), work.data_ptr(), work.numel(),
+              torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def adi_batched(vertices, R_est, t_est, R_gt, t_gt):
+    """adi(pts_est, pts_gt) (utils.py:60-63) for n pose pairs of one mesh in one launch, estimate first as in the
+    reference: vertices (3,N) or (4,N), R_* (n,3,3), t_* (n,3,1) or (n,3) -> (n,) float64 ndarray, the mean distance
+    from each ground-truth-posed vertex to the nearest estimate-posed vertex (ADD-S).  Exhaustive in fp64: the same
+    nearest-neighbour distances as the reference's KD-tree."""
+    v, off = _pack_models([vertices])
+    Rt_gt, Rt_pr = _pack_poses(R_gt, t_gt, R_est, t_est)
+    n = len(Rt_gt)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    vd = _to_dev_f64(v)
+    which = torch.zeros(n, dtype=torch.int32, device=vd.device)
+    return adds_device(vd, torch.as_tensor(off).to(vd.device), which, _to_dev_f64(Rt_pr), _to_dev_f64(Rt_gt),
+                       int(off[1])).cpu().numpy()
+
+
+def pose_errors_models_batched(models, model_index, R_gt, t_gt, R_pr, t_pr, internal_calibration, symmetric=()):
+    """pose_errors_batched with one mesh per pose, plus ADD-S for the symmetric ones.
+
+    models: a sequence of (3,N) / (4,N) meshes; model_index (n,) the mesh of each pose; R_*, t_*, K as in
+    pose_errors_batched; symmetric: the mesh indices scored with ADD-S.  -> float64 ndarray (n,5): columns 0-3 are
+    pose_errors_batched's, column 4 is ADD-S (adi(estimate, ground truth)) for the poses of a symmetric mesh and NaN for
+    the others - only those poses go to ssp_adds_errors.  Argument errors raise ValueError before the GPU is touched."""
+    v, off = _pack_models(models)
+    nM = len(off) - 1
+    Rt_gt, Rt_pr = _pack_poses(R_gt, t_gt, R_pr, t_pr)
+    n = len(Rt_gt)
+    idx = np.asarray(model_index.cpu() if torch.is_tensor(model_index) else model_index).reshape(-1)
+    if len(idx) != n:
+        raise ValueError("model_index must hold one entry per pose (%d poses, %d entries)" % (n, len(idx)))
+    if n and (np.any(idx != np.floor(idx)) or idx.min() < 0 or idx.max() >= nM):
+        raise ValueError("model_index values must be integers in [0, %d)" % nM)
+    idx = idx.astype(np.int32)
+    sym = sorted(set(int(s) for s in symmetric))
+    if any(s < 0 or s >= nM for s in sym):
+        raise ValueError("symmetric names a model that was not given (%d models)" % nM)
+    Kh = np.asarray(internal_calibration.cpu() if torch.is_tensor(internal_calibration) else internal_calibration,
+                    dtype=np.float64).reshape(-1, 9)
+    if Kh.shape[0] not in (1, n):
+        raise ValueError("internal_calibration must be (3,3) or (n,3,3)")
+    res = np.full((n, 5), np.nan)
+    if n == 0:
+        return res
+    vd, Rg, Rp = _to_dev_f64(v), _to_dev_f64(Rt_gt), _to_dev_f64(Rt_pr)
+    offd, idxd = torch.as_tensor(off).to(vd.device), torch.as_tensor(idx).to(vd.device)
+    err = pose_errors_models_device(vd, offd, idxd, Rg, Rp, _to_dev_f64(Kh))
+    rows = np.nonzero(np.isin(idx, sym))[0]
+    if len(rows):
+        sel = torch.as_tensor(rows).to(vd.device)
+        adds = adds_device(vd, offd, idxd[sel].contiguous(), Rp[sel].contiguous(), Rg[sel].contiguous(),
+                           int(np.diff(off)[sym].max()))
+        res[rows, 4] = adds.cpu().numpy()
+    res[:, :4] = err.cpu().numpy()
+    return res
+
+
 def calc_pts_diameter_gpu(pts):
     """calc_pts_diameter (utils.py:50-58) on the device: exact fp64 maximum over all N(N+1)/2 pairs, one launch
     instead of the reference's N numpy passes (minutes for a 6 k vertex mesh)."""

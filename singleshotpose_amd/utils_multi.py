@@ -10,8 +10,12 @@ box has that class; `max_cls_conf` is NOT reset per image (SURVEY.md appendix C.
 match_multi_region_boxes / evaluate_multi_batched are the batched validator (valid_multi.py:94-149 for every image and
 every ground truth of a batch, all object classes in one pass): ssp_region_match_multi selects the box of each ground
 truth on the device, one fused ssp_pnp_batched launch and one ssp_pose_errors launch follow, one copy returns the result.
+Given one mesh per class ({class id: vertices}) every ground truth is scored against its own object model
+(ssp_pose_errors_models), the symmetric classes with ADD-S as well (ssp_adds_errors); summarize_multi turns the result
+into the per-class accuracies the reference's validators print.
 """
 import collections
+import collections.abc
 import sys
 
 import numpy as np
@@ -19,7 +23,8 @@ import torch
 
 from . import _lib
 from .utils import *  # noqa: F401,F403
-from .utils import _to_dev_f64, get_3D_corners, pnp_device, pose_errors_device
+from .utils import (_pack_models, _to_dev_f64, adds_device, get_3D_corners, pnp_device, pose_errors_device,
+                    pose_errors_models_device)
 
 MAX_GT = 50      # label rows per image (dataset_multi.py pads every label file to 50 rows)
 
@@ -167,8 +172,28 @@ def match_multi_region_boxes(output, target, conf_thresh, num_classes, num_keypo
     return MultiMatch(rows[..., :2 * K + 3], meta[..., 0], meta[..., 1], rows[..., 2 * K + 3])
 
 
+def _object_points(vertices):
+    """The nine PnP object points of a mesh, (9,3) float32: the centroid 0 and the 8 corners of get_3D_corners
+    (valid_multi.py:135)."""
+    corners3D = get_3D_corners(np.asarray(vertices.cpu() if torch.is_tensor(vertices) else vertices))
+    return np.array(np.transpose(np.concatenate((np.zeros((3, 1)), corners3D[:3, :]), axis=1)), dtype='float32')
+
+
+def _class_models(vertices, symmetric):
+    """{class id: mesh} -> (sorted class ids, concatenated (sumN,3) float64 mesh, (nM+1,) int32 offsets, (nM,9,3) float64
+    PnP object points, sorted symmetric model indices); ValueError before anything touches the GPU."""
+    classes = sorted(int(c) for c in vertices.keys())
+    v, off = _pack_models([vertices[c] for c in classes])          # raises on an empty mapping / a mesh of another shape
+    obj = np.stack([_object_points(vertices[c]) for c in classes]).astype(np.float64)
+    sym = sorted(set(int(c) for c in (symmetric if symmetric is not None else ())))
+    missing = [c for c in sym if c not in classes]
+    if missing:
+        raise ValueError("symmetric names class %s, which has no object model" % missing)
+    return classes, v, off, obj, [classes.index(c) for c in sym]
+
+
 def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoints, anchors, num_anchors, vertices,
-                           intrinsic_calibration, im_width, im_height, only_objectness=0):
+                           intrinsic_calibration, im_width, im_height, only_objectness=0, symmetric=None):
     """valid_multi.py:94-149 for all images and all ground truths of a batch, every object class in the same pass.
 
     match_multi_region_boxes, then on the device: both corner sets denormalised in float32, fix_corner_order on the
@@ -181,8 +206,25 @@ def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoin
 
     Returns numpy arrays over the n surviving ground truths, in (image, row) order: image, gt (label row), cls, source
     (n,) ints; corners2D_pr (n,9,2) float32 pixels; match (n,) float32; R_gt, R_pr (n,3,3), t_gt, t_pr (n,3,1) float64;
-    errors (n,4) float64 in pose_errors_batched's column order."""
+    errors (n,4) float64 in pose_errors_batched's column order.
+
+    ONE MESH PER CLASS.  `vertices` may be a mapping {class id: (3|4, N) mesh} instead of one mesh for the whole batch -
+    the reference's validator is run once per object and loads that object's mesh, corners and diameter each time
+    (valid_multi.py:47-50).  Every ground truth and its prediction then use the object points of their own class in the
+    same single PnP launch and the vertices of their own class in one ssp_pose_errors_models launch; ground truths of a
+    class WITHOUT a model are left out of the result (the reference scores 6 of the 13 classes of yolo-pose-multi.cfg the
+    same way).  symmetric: an iterable of class ids scored with ADD-S as well (adi(estimate, ground truth),
+    utils_multi.py:66-69; only their rows go to ssp_adds_errors): `errors` is then (n,5), column 4 ADD-S for those
+    classes and NaN for the others.  The meshes, offsets and object points are assembled once per call on the host and
+    uploaded in one copy.  An empty mapping, a mesh that is not (3|4, N) and a symmetric id without a model raise
+    ValueError before the GPU is touched; a single mesh with symmetric=None takes the single-mesh path unchanged."""
     K = num_keypoints
+    models = None
+    if isinstance(vertices, collections.abc.Mapping):
+        models = _class_models(vertices, symmetric)
+    elif symmetric is not None:
+        raise ValueError("symmetric needs one object model per class: pass vertices as {class id: mesh}")
+    ncol = 5 if symmetric is not None else 4
     out = _head_f32(output, num_classes, K, num_anchors, "evaluate_multi_batched")
     dev = out.device
     lab = _labels(target, out.size(0), K)
@@ -192,7 +234,8 @@ def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoin
     for b in range(head.shape[0]):
         stop = np.nonzero(head[b, :, 1] == 0)[0]
         for k in range(int(stop[0]) if len(stop) else MAX_GT):
-            if np.isfinite(head[b, k, 0]) and 0 <= int(head[b, k, 0]) < num_classes:
+            if np.isfinite(head[b, k, 0]) and 0 <= int(head[b, k, 0]) < num_classes and (
+                    models is None or int(head[b, k, 0]) in models[0]):
                 image.append(b)
                 gt.append(k)
     image, gt = np.asarray(image, dtype=np.int64), np.asarray(gt, dtype=np.int64)
@@ -201,24 +244,48 @@ def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoin
     if n == 0:
         z = np.zeros
         return MultiEval(image, gt, cls, z(0, dtype=np.int64), z((0, K, 2), dtype=np.float32), z(0, dtype=np.float32),
-                         z((0, 3, 3)), z((0, 3, 1)), z((0, 3, 3)), z((0, 3, 1)), z((0, 4)))
-    bi, ki = torch.as_tensor(image).to(dev), torch.as_tensor(gt).to(dev)
+                         z((0, 3, 3)), z((0, 3, 1)), z((0, 3, 3)), z((0, 3, 1)), z((0, ncol)))
+    if models is None:
+        bi, ki = torch.as_tensor(image).to(dev), torch.as_tensor(gt).to(dev)
+    else:
+        # one upload of the indices (image, label row, model of every ground truth, rows of the symmetric classes) and
+        # one of the floats (meshes back to back, object points, offsets: integers below 2^53 are exact in float64)
+        classes, mesh, off, objs, sym = models
+        which = np.searchsorted(classes, cls)
+        sym_rows = np.nonzero(np.isin(which, sym))[0]
+        idx = torch.as_tensor(np.concatenate((image, gt, which, sym_rows)).astype(np.int64)).to(dev)
+        bi, ki, pm, sel = idx[:n], idx[n:2 * n], idx[2 * n:3 * n], idx[3 * n:]
+        blob = torch.as_tensor(np.concatenate((mesh.reshape(-1), objs.reshape(-1), off.astype(np.float64)))).to(dev)
+        v = blob[:mesh.size].reshape(-1, 3)
+        objd = blob[mesh.size:mesh.size + objs.size].reshape(-1, K, 3)
+        offd = blob[mesh.size + objs.size:].to(torch.int32)
     scale = torch.tensor([float(im_width), float(im_height)], dtype=torch.float32, device=dev)
     order = torch.tensor([0, 1, 3, 5, 7, 2, 4, 6, 8], device=dev)                      # fix_corner_order
     tgt = lab.to(device=dev, dtype=torch.float32)
     c_gt = (tgt[bi, ki, 1:2 * K + 1].reshape(n, K, 2) * scale)[:, order]
     c_pr = m.boxes[bi, ki, :2 * K].reshape(n, K, 2) * scale
-    corners3D = get_3D_corners(np.asarray(vertices.cpu() if torch.is_tensor(vertices) else vertices))
-    obj = np.array(np.transpose(np.concatenate((np.zeros((3, 1)), corners3D[:3, :]), axis=1)), dtype='float32')
     K32 = np.array(np.asarray(intrinsic_calibration.cpu() if torch.is_tensor(intrinsic_calibration)
                               else intrinsic_calibration), dtype='float32')
-    p3 = torch.as_tensor(obj.astype(np.float64)).to(dev).expand(2 * n, K, 3).contiguous()
+    if models is None:
+        p3 = torch.as_tensor(_object_points(vertices).astype(np.float64)).to(dev).expand(2 * n, K, 3).contiguous()
+    else:
+        p3 = objd[pm].repeat(2, 1, 1).contiguous()           # ground truths first, predictions after: the same points twice
     Kt = torch.as_tensor(K32.astype(np.float64)).to(dev).expand(2 * n, 3, 3).contiguous()
     Rt = pnp_device(p3, torch.cat((c_gt, c_pr), dim=0).to(torch.float64).contiguous(), Kt)
-    v = _to_dev_f64(vertices)
-    if v.dim() != 2 or v.size(0) not in (3, 4):
-        raise ValueError("vertices must be (3,N) or (4,N)")
-    err = pose_errors_device(v[:3].t().contiguous(), Rt[:n], Rt[n:], _to_dev_f64(intrinsic_calibration).reshape(1, 9))
+    Kd = _to_dev_f64(intrinsic_calibration).reshape(1, 9)
+    if models is None:
+        v = _to_dev_f64(vertices)
+        if v.dim() != 2 or v.size(0) not in (3, 4):
+            raise ValueError("vertices must be (3,N) or (4,N)")
+        err = pose_errors_device(v[:3].t().contiguous(), Rt[:n], Rt[n:], Kd)
+    else:
+        pm32 = pm.to(torch.int32)
+        err = pose_errors_models_device(v, offd, pm32, Rt[:n].contiguous(), Rt[n:].contiguous(), Kd)
+        if symmetric is not None:
+            err = torch.cat((err, torch.full((n, 1), float('nan'), dtype=torch.float64, device=dev)), dim=1)
+            if len(sym_rows):
+                err[sel, 4] = adds_device(v, offd, pm32[sel].contiguous(), Rt[n:][sel].contiguous(), Rt[:n][sel].contiguous(),
+                                          int(np.diff(off)[sym].max()))
     packed = torch.cat((m.source[bi, ki].to(torch.float64).unsqueeze(1), m.match[bi, ki].to(torch.float64).unsqueeze(1),
                         c_pr.reshape(n, 2 * K).to(torch.float64), Rt[:n], Rt[n:], err), dim=1).cpu().numpy()
     keep = packed[:, 0] != 0
@@ -228,4 +295,28 @@ def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoin
                      packed[:, 2:o].astype(np.float32).reshape(-1, K, 2), packed[:, 1].astype(np.float32),
                      packed[:, o:o + 9].reshape(-1, 3, 3).copy(), packed[:, o + 9:o + 12].reshape(-1, 3, 1).copy(),
                      packed[:, o + 12:o + 21].reshape(-1, 3, 3).copy(), packed[:, o + 21:o + 24].reshape(-1, 3, 1).copy(),
-                     packed[:, o + 24:o + 28].copy())
+                     packed[:, o + 24:o + 24 + ncol].copy())
+
+
+def summarize_multi(ev, diameters, px=5.0, add_frac=0.1, cm=0.05, deg=5.0):
+    """Per-class accuracies of an evaluate_multi_batched result, host numpy: {class id: dict(count, acc_px, acc_add,
+    acc_cm_deg)} for every class of `diameters` ({class id: model diameter}), in percent with the reference's
+    eps = 1e-5 in the denominator (valid_multi.py:154-156, valid.py's acc / acc3d10 / acc5cm5deg):
+      acc_px      pixel_dist <= px
+      acc_add     ADD(-S) <= add_frac * diameter: ADD-S (column 4) where it is finite, vertex_dist (column 1) otherwise
+      acc_cm_deg  trans_dist <= cm and angle_dist <= deg
+    A class without rows has count 0 and accuracies 0."""
+    eps = 1e-5
+    errors, cls = np.asarray(ev.errors, dtype=np.float64), np.asarray(ev.cls)
+    add = errors[:, 1].copy()
+    if errors.shape[1] > 4:
+        adds = np.isfinite(errors[:, 4])
+        add[adds] = errors[adds, 4]
+    res = {}
+    for c in sorted(diameters):
+        rows = cls == c
+        count = int(rows.sum())
+        pct = lambda hit: int(np.count_nonzero(hit[rows])) * 100. / (count + eps)
+        res[c] = dict(count=count, acc_px=pct(errors[:, 0] <= px), acc_add=pct(add <= add_frac * float(diameters[c])),
+                      acc_cm_deg=pct((errors[:, 2] <= cm) & (errors[:, 3] <= deg)))
+    return res

@@ -2,7 +2,8 @@
 """Latency-bound pieces of the path (SURVEY.md section 8(d) config 4 and the 'report us per call' rows): eval-mode
 forward at 672x672 (valid.py's test size), decode, batched PnP, batched pose errors, RegionLoss, fused SGD, and the
 multi-object validator (eval_multi: evaluate_multi_batched against today's per-ground-truth host route).
-Prints one JSON object; numbers go to DESIGN.md section 3.  `infer_bench.py eval_multi` runs that line alone."""
+Prints one JSON object; numbers go to DESIGN.md section 3.  `infer_bench.py eval_multi` runs that line alone;
+`infer_bench.py adds` times ADD-S and the per-class validator."""
 import json
 import os
 import sys
@@ -77,10 +78,81 @@ def eval_multi(res):
     res['eval_multi_b64_13x13_2gt_per_gt_host_route'] = {'us': round(timed(per_gt, 2, warm=1) * 1e6, 1), 'ground_truths': per_gt()}
 
 
+def adds(res):
+    """N = 5841 vertices (the ape mesh), n = 128 poses.  One adds_device call (ssp_adds_errors: n * N^2 = 4.4 G fp64 pair
+    evaluations) on device tensors; ssp_pose_errors_models against ssp_pose_errors on the same poses; the host route,
+    utils.adi (scipy KD-tree) once per pose, where scipy imports; and the whole validator call of eval_multi() with one
+    mesh for six of the 13 classes and one of them symmetric, beside the single-mesh call in the same run."""
+    from singleshotpose_amd import _lib
+    from singleshotpose_amd import utils as U
+    from singleshotpose_amd import utils_multi as UM
+    rs = np.random.RandomState(0)
+    N, n = 5841, 128
+    half = np.array([0.038, 0.039, 0.046])
+    verts = rs.uniform(-1, 1, (N, 3)) * half
+    R = np.stack([np.linalg.qr(rs.standard_normal((3, 3)))[0] for _ in range(n)])
+    R *= np.sign(np.linalg.det(R))[:, None, None]
+    t = np.stack([np.array([rs.uniform(-.1, .1), rs.uniform(-.1, .1), rs.uniform(.6, 1.2)]) for _ in range(n)])
+    def turn(angle):
+        a = rs.standard_normal(3)
+        a /= np.linalg.norm(a)
+        X = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        return np.eye(3) + np.sin(angle) * X + (1 - np.cos(angle)) * X.dot(X)
+    small = np.stack([turn(0.05) for _ in range(n)])          # the estimate: 3 degrees and up to 1 cm off
+    R2, t2 = np.einsum('nij,njk->nik', small, R), t + rs.uniform(-0.01, 0.01, (n, 3))
+    dev = torch.device('cuda', 0)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+    v, off, pm = up(verts), up(np.array([0, N], dtype=np.int32)), up(np.zeros(n, dtype=np.int32))
+    Rt_gt, Rt_pr = up(np.concatenate((R.reshape(n, 9), t), axis=1)), up(np.concatenate((R2.reshape(n, 9), t2), axis=1))
+    Kc = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.5704, 242.0489], [0.0, 0.0, 1.0]])
+    Kd = up(Kc.reshape(1, 9))
+    q = lambda count: _lib.query('ssp_adds_workspace_doubles', 1, count)
+    res['adds_chunk_vertices'] = next(c for c in (256, 512, 1024, 2048) if q(c) == 1 and q(c + 1) == 2)
+    dt = timed(lambda: U.adds_device(v, off, pm, Rt_pr, Rt_gt, N), 10)
+    res['adds_device_128x5841'] = {'us': round(dt * 1e6, 1), 'pairs_per_s': round(n * N * N / dt, -6)}
+    dt = timed(lambda: U.pose_errors_models_device(v, off, pm, Rt_gt, Rt_pr, Kd), 20)
+    res['pose_errors_models_128x5841'] = {'us': round(dt * 1e6, 1)}
+    dt = timed(lambda: U.pose_errors_device(v, Rt_gt, Rt_pr, Kd), 20)
+    res['pose_errors_128x5841'] = {'us': round(dt * 1e6, 1)}
+    dt = timed(lambda: U.adi_batched(verts.T, R2, t2, R, t), 10)
+    res['adi_batched_128x5841_incl_h2d_d2h'] = {'us': round(dt * 1e6, 1)}
+    gpu = U.adi_batched(verts.T, R2, t2, R, t)
+    try:
+        import scipy  # noqa: F401
+        t0 = time.perf_counter()
+        host = np.array([U.adi(verts.dot(R2[i].T) + t2[i], verts.dot(R[i].T) + t[i]) for i in range(n)])
+        res['adi_host_scipy_128x5841'] = {'us': round((time.perf_counter() - t0) * 1e6, 1),
+                                          'max_abs_diff_to_gpu': float(np.abs(host - gpu).max())}
+    except ImportError:
+        res['adi_host_scipy_128x5841'] = 'scipy is not installed'
+    # the whole validator call: eval_multi()'s inputs, one 5841-vertex mesh for six classes, one of them symmetric
+    B, nA, nC, K, grid, thresh = 64, 5, 13, 9, 13, 0.05
+    anchors = [1.4820, 2.2412, 2.0501, 3.1265, 2.3946, 4.6891, 3.1018, 3.9910, 3.4879, 5.8851]
+    g = torch.Generator().manual_seed(0)
+    head = torch.randn(B, nA, 2 * K + 1 + nC, grid, grid, generator=g)
+    head[:, :, 2 * K] -= 3.0
+    head = head.view(B, -1, grid, grid).cuda()
+    tgt = np.zeros((B, 50, 2 * K + 3), dtype=np.float32)
+    for b in range(B):
+        for k in range(2):
+            c = rs.uniform(0.3, 0.7, 2)
+            tgt[b, k, 0] = rs.randint(0, 6)
+            tgt[b, k, 1:2 * K + 1] = (c[None, :] + rs.uniform(-0.1, 0.1, (K, 2))).reshape(-1)
+    target = torch.from_numpy(tgt.reshape(B, -1))
+    meshes = {c: (verts * (1.0 + 0.1 * c)).T for c in range(6)}
+    call = lambda vertices, **kw: UM.evaluate_multi_batched(head, target, thresh, nC, K, anchors, nA, vertices, Kc, 640, 480, **kw)
+    rows = len(call(meshes).image)
+    nsym = int((call(meshes).cls == 3).sum())
+    res['eval_multi_b64_13x13_2gt_single_mesh'] = {'us': round(timed(lambda: call(meshes[0]), 20) * 1e6, 1), 'ground_truths': rows}
+    res['eval_multi_b64_13x13_2gt_6_meshes'] = {'us': round(timed(lambda: call(meshes), 20) * 1e6, 1), 'ground_truths': rows}
+    res['eval_multi_b64_13x13_2gt_6_meshes_1_symmetric'] = {'us': round(timed(lambda: call(meshes, symmetric=[3]), 20) * 1e6, 1),
+                                                            'ground_truths': rows, 'adds_rows': nsym}
+
+
 def main():
-    if sys.argv[1:] == ['eval_multi']:
+    if sys.argv[1:] in (['eval_multi'], ['adds']):
         res = {}
-        eval_multi(res)
+        (eval_multi if sys.argv[1] == 'eval_multi' else adds)(res)
         print(json.dumps(res))
         return
     from singleshotpose_amd import utils as U
