@@ -37,8 +37,11 @@ def _residual_jac(R, t, X, uv, fx, fy, cx, cy):
     return err, J
 
 
-def solve_pnp_ref(X, uv, K, max_iter=20):
-    """X (N,3), uv (N,2), K (3,3) -> R (3,3), t (3,1) float64."""
+def solve_pnp_ref(X, uv, K, max_iter=20, dlt_perturb=None):
+    """X (N,3), uv (N,2), K (3,3) -> R (3,3), t (3,1) float64.
+
+    dlt_perturb (12,), optional: added to the unit DLT null vector before it is used.  Test infrastructure: it shows how
+    far the answer depends on the last bits of the initialisation (tests/pnp_cases.py's include mask)."""
     X = np.asarray(X, np.float64)
     uv = np.asarray(uv, np.float64)
     K = np.asarray(K, np.float64)
@@ -50,7 +53,8 @@ def solve_pnp_ref(X, uv, K, max_iter=20):
     L[0::2, 0:4], L[0::2, 8:12] = Xh, -xn[:, None] * Xh
     L[1::2, 4:8], L[1::2, 8:12] = Xh, -yn[:, None] * Xh
     _, _, Vt = np.linalg.svd(L.T.dot(L))
-    RRt = Vt[11].reshape(3, 4)
+    v = Vt[11] if dlt_perturb is None else Vt[11] + np.asarray(dlt_perturb, np.float64)
+    RRt = v.reshape(3, 4)
     RR, tt = RRt[:, :3], RRt[:, 3]
     if np.linalg.det(RR) < 0:
         RR, tt = -RR, -tt

@@ -14,13 +14,19 @@
 //
 // Everything a thread touches is indexed at compile time (fully unrolled loops over 12 / 6 / 3), so the 12 x 12 normal
 // matrix, its Cholesky factor and the 6 x 6 LM system live in VGPRs: the first version kept them in dynamically indexed
-// arrays, i.e. in scratch memory, and took 2.1 ms for one pose.  The DLT null vector comes from inverse iteration on
-// the Cholesky-factored (lightly shifted) normal matrix instead of a full Jacobi eigen-decomposition (the smallest
-// eigen-pair is all that is used; the LM refinement that follows makes the result independent of how it was found),
-// the nearest rotation from the Newton iteration for the polar factor, the LM step from an unpivoted 6 x 6 Cholesky.
+// arrays, i.e. in scratch memory, and took 2.1 ms for one pose.  The DLT null vector comes from shifted inverse iteration
+// on the Cholesky-factored normal matrix instead of a full eigen-decomposition (the smallest eigen-pair is all that is
+// used), the nearest rotation from the scaled Newton iteration for the polar factor, the LM step from an unpivoted
+// 6 x 6 Cholesky.  Both iterations run to convergence, to what an SVD returns: the LM refinement is capped at max_iter
+// steps and the objective has more than one local minimum (the mirrored pose among them), so the result DOES depend on
+// the start.  With 16 unshifted inverse iterations and 12 unscaled Newton steps, as this file once had, one problem in
+// eight at 5 px of corner noise ended at another pose than OpenCV's algorithm (tests/test_gpu_pnp.py).
 #include "ssp_common.h"
 
 #define PNP_MAXN 16
+
+#define PNP_DLT_PASSES 24    // bound on the shifted inverse-iteration passes (6..9 are used with 2..10 px of corner noise)
+#define PNP_POLAR_STEPS 40   // bound on the scaled Newton steps of the polar factor (<= 8 are used)
 
 #define TRI(a, b) ((a) * ((a) + 1) / 2 + (b))   // packed lower triangle, a >= b
 
@@ -92,6 +98,18 @@ __device__ __forceinline__ double reproj(const double* R, const double* t, const
   return e2;
 }
 
+// the two rows of the DLT system that point i contributes: [P 1 | 0 | -xn (P 1)] and [0 | P 1 | -yn (P 1)]
+__device__ __forceinline__ void dlt_rows(const double* __restrict__ X, const double* __restrict__ uv, int i, double fx,
+                                         double fy, double cx, double cy, double* r0, double* r1) {
+  const double xn = (uv[2 * i] - cx) / fx, yn = (uv[2 * i + 1] - cy) / fy;
+  const double P[4] = {X[3 * i], X[3 * i + 1], X[3 * i + 2], 1.0};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    r0[k] = P[k]; r0[4 + k] = 0.0; r0[8 + k] = -xn * P[k];
+    r1[k] = 0.0;  r1[4 + k] = P[k]; r1[8 + k] = -yn * P[k];
+  }
+}
+
 // in-place Cholesky of a packed lower-triangular SPD matrix (compile-time n); false when a pivot is not positive
 template <int n>
 __device__ __forceinline__ bool chol_packed(double* A) {
@@ -145,42 +163,88 @@ __global__ void __launch_bounds__(64) pnp_kernel(const double* __restrict__ pts3
   const double* Km = Kmat + (int64_t)id * 9;
   const double fx = Km[0], fy = Km[4], cx = Km[2], cy = Km[5];
 
-  // ---- DLT: L = M^T M of the 2N x 12 system (packed lower triangle) ----
-  double L[78];
-#pragma unroll
-  for (int i = 0; i < 78; ++i) L[i] = 0.0;
+  // ---- DLT: smallest eigenvector of L = M^T M of the 2N x 12 system ----
+  // Inverse iteration on the Cholesky-factored L - s I, run to convergence.  Its factor is (l_1 - s) / (l_2 - s), and
+  // with noisy corners l_1 / l_2 reaches 0.95, so the shift s moves up towards l_1 as the vector converges.  With rho the
+  // Rayleigh quotient (>= l_1) and eps = |L v - rho v|, an eigenvalue lies within eps of rho, so rho - 2 eps is below
+  // l_1 once v is nearer to the first eigenvector than to any other: the angle a then contracts like a -> a (2a)^2 per
+  // pass of two solves.  A shift that overshoots l_1 makes the factorisation hit a non-positive pivot; the next try is
+  // then halfway back to the last shift that factored.  Every pass rebuilds L from the points (the factor overwrites it):
+  // one body, run-time trip counts, nothing indexed at run time.  The start s = -mu (mu ~ 1e-11 of the mean eigenvalue)
+  // keeps the factorisation positive when the data are exact and L is singular to rounding.
+  double tr = 0.0;
   for (int i = 0; i < N; ++i) {
     const double xn = (uv[2 * i] - cx) / fx, yn = (uv[2 * i + 1] - cy) / fy;
-    const double P[4] = {X[3 * i], X[3 * i + 1], X[3 * i + 2], 1.0};
-    double r0[12], r1[12];
+    const double P0 = X[3 * i], P1 = X[3 * i + 1], P2 = X[3 * i + 2];
+    tr += (P0 * P0 + P1 * P1 + P2 * P2 + 1.0) * (2.0 + xn * xn + yn * yn);
+  }
+  double v[12] = {0.3010, -0.5236, 0.1729, 0.4142, -0.2718, 0.1618, 0.5772, -0.3679, 0.2236, -0.1414, 0.6931, 0.3333};
+  double s_lo = -1e-11 * tr / 12.0, s_try = s_lo;
+  bool last = false, factored = false;
+  for (int pass = 0; pass < PNP_DLT_PASSES; ++pass) {
+    double L[78];   // packed lower triangle
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      r0[k] = P[k]; r0[4 + k] = 0.0; r0[8 + k] = -xn * P[k];
-      r1[k] = 0.0;  r1[4 + k] = P[k]; r1[8 + k] = -yn * P[k];
+    for (int i = 0; i < 78; ++i) L[i] = 0.0;
+    for (int i = 0; i < N; ++i) {
+      double r0[12], r1[12];
+      dlt_rows(X, uv, i, fx, fy, cx, cy, r0, r1);
+#pragma unroll
+      for (int a = 0; a < 12; ++a)
+#pragma unroll
+        for (int b = 0; b <= a; ++b) L[TRI(a, b)] += r0[a] * r0[b] + r1[a] * r1[b];
     }
 #pragma unroll
-    for (int a = 0; a < 12; ++a)
+    for (int a = 0; a < 12; ++a) L[TRI(a, a)] -= s_try;
+    if (!chol_packed<12>(L)) {
+      if (!(s_try > s_lo)) break;   // not even the start factors: non-finite input
+      s_try = 0.5 * (s_lo + s_try);
+      continue;
+    }
+    s_lo = s_try;
+    factored = true;
+    double diff2 = 0.0;
+    for (int it = 0; it < 2; ++it) {
+      double vp[12];
 #pragma unroll
-      for (int b = 0; b <= a; ++b) L[TRI(a, b)] += r0[a] * r0[b] + r1[a] * r1[b];
+      for (int a = 0; a < 12; ++a) vp[a] = v[a];
+      chol_solve<12>(L, v);
+      double nn = 0.0;
+#pragma unroll
+      for (int a = 0; a < 12; ++a) nn += v[a] * v[a];
+      const double inv = 1.0 / sqrt(nn);
+      diff2 = 0.0;
+#pragma unroll
+      for (int a = 0; a < 12; ++a) {
+        v[a] *= inv;
+        diff2 += (v[a] - vp[a]) * (v[a] - vp[a]);
+      }
+    }
+    if (last) break;
+    // the last solve moved v by less than 1e-14: converged (the error is below that times factor / (1 - factor));
+    // one more pass at the tighter shift takes it to rounding
+    last = diff2 < 1e-28;
+    double rho = 0.0, w[12];
+#pragma unroll
+    for (int a = 0; a < 12; ++a) w[a] = 0.0;
+    for (int i = 0; i < N; ++i) {
+      double r0[12], r1[12];
+      dlt_rows(X, uv, i, fx, fy, cx, cy, r0, r1);
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int a = 0; a < 12; ++a) { a0 += r0[a] * v[a]; a1 += r1[a] * v[a]; }
+      rho += a0 * a0 + a1 * a1;
+#pragma unroll
+      for (int a = 0; a < 12; ++a) w[a] += r0[a] * a0 + r1[a] * a1;
+    }
+    double eps = 0.0;
+#pragma unroll
+    for (int a = 0; a < 12; ++a) eps += (w[a] - rho * v[a]) * (w[a] - rho * v[a]);
+    eps = sqrt(eps);
+    s_try = fmax(s_lo, rho - fmax(2.0 * eps, 1e-13 * tr));
   }
-  // smallest eigenvector by inverse iteration on L + mu I (mu ~ 1e-11 of the mean eigenvalue keeps the factorisation
-  // positive when the data are exact and L is singular to rounding; convergence factor (l_min + mu) / (l_2 + mu))
-  double tr = 0.0;
+  if (!factored) {   // a NaN or Inf corner: the row's pose is NaN, not the start vector refined by nothing
 #pragma unroll
-  for (int a = 0; a < 12; ++a) tr += L[TRI(a, a)];
-  const double mu = 1e-11 * tr / 12.0;
-#pragma unroll
-  for (int a = 0; a < 12; ++a) L[TRI(a, a)] += mu;
-  chol_packed<12>(L);
-  double v[12] = {0.3010, -0.5236, 0.1729, 0.4142, -0.2718, 0.1618, 0.5772, -0.3679, 0.2236, -0.1414, 0.6931, 0.3333};
-  for (int it = 0; it < 16; ++it) {
-    chol_solve<12>(L, v);
-    double nn = 0.0;
-#pragma unroll
-    for (int a = 0; a < 12; ++a) nn += v[a] * v[a];
-    const double inv = 1.0 / sqrt(nn);
-#pragma unroll
-    for (int a = 0; a < 12; ++a) v[a] *= inv;
+    for (int a = 0; a < 12; ++a) v[a] = __builtin_nan("");
   }
   double RR[9], tt[3];
 #pragma unroll
@@ -201,19 +265,35 @@ __global__ void __launch_bounds__(64) pnp_kernel(const double* __restrict__ pts3
 #pragma unroll
   for (int i = 0; i < 9; ++i) sc += RR[i] * RR[i];
   sc = sqrt(sc);
-  // nearest rotation = orthogonal polar factor of RR: Newton iteration Q <- (Q + Q^-T) / 2 from Q0 = RR * sqrt(3) / |RR|
+  // nearest rotation = orthogonal polar factor of RR (det > 0): Newton iteration Q <- (g Q + Q^-T / g) / 2 with the
+  // Frobenius scaling g = (|Q^-T| / |Q|)^(1/2), run until a step moves Q by less than 1e-15.  The scaling brings any
+  // condition number to ~1 in a few steps (cond(RR) reaches 2e4 with noisy corners; unscaled, each step only halves it).
   double R[9], t[3];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = RR[i] * (sqrt(3.0) / sc);
-  for (int it = 0; it < 12; ++it) {
+  for (int i = 0; i < 9; ++i) R[i] = RR[i];
+  for (int it = 0; it < PNP_POLAR_STEPS; ++it) {
     double C[9];   // cofactor matrix = det * Q^-T
     C[0] = R[4] * R[8] - R[5] * R[7]; C[1] = R[5] * R[6] - R[3] * R[8]; C[2] = R[3] * R[7] - R[4] * R[6];
     C[3] = R[2] * R[7] - R[1] * R[8]; C[4] = R[0] * R[8] - R[2] * R[6]; C[5] = R[1] * R[6] - R[0] * R[7];
     C[6] = R[1] * R[5] - R[2] * R[4]; C[7] = R[2] * R[3] - R[0] * R[5]; C[8] = R[0] * R[4] - R[1] * R[3];
     const double d = R[0] * C[0] + R[1] * C[1] + R[2] * C[2];
     const double id_ = 1.0 / d;
+    double nq = 0.0, ni = 0.0;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = 0.5 * (R[i] + C[i] * id_);
+    for (int i = 0; i < 9; ++i) {
+      C[i] *= id_;
+      nq += R[i] * R[i];
+      ni += C[i] * C[i];
+    }
+    const double g = sqrt(sqrt(ni / nq)), ig = 1.0 / g;
+    double diff2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const double q = 0.5 * (g * R[i] + ig * C[i]);
+      diff2 += (q - R[i]) * (q - R[i]);
+      R[i] = q;
+    }
+    if (diff2 < 1e-30) break;
   }
 #pragma unroll
   for (int i = 0; i < 3; ++i) t[i] = tt[i] * (sqrt(3.0) / sc);

@@ -2,7 +2,9 @@
 un-versioned `opencv-python`, /root/reference/README.md:30, no wheel, no network).  The first box that has it closes
 SURVEY.md section 8(c)'s "parity unpinned" for a17: ssp_pnp_batched and oracle/pnp_ref.py against
 cv2.solvePnP(..., flags=SOLVEPNP_ITERATIVE) + cv2.Rodrigues exactly as /root/reference/utils.py:86-100 calls them, on
-the 64 synthetic LINEMOD-range poses of SURVEY.md section 8(d) config 4; bar = north_star's 1e-3 px reprojection."""
+the 64 synthetic LINEMOD-range poses of SURVEY.md section 8(d) config 4; bar = north_star's 1e-3 px reprojection.
+The noisy-corner populations of tests/pnp_cases.py (2 / 5 / 10 px, N = 6 .. 16; fixture tests/golden/pnp_noise.npz) go
+through the same diff: the oracle's stored poses and the kernel's against cv2's, on the included problems."""
 import importlib.util
 
 import numpy as np
@@ -70,3 +72,33 @@ def test_hip_pnp_matches_opencv():
     for uv, R1, t1 in zip(uvs, Rs, ts):
         R0, t0 = _cv2_pnp(cv2, X, uv, K)
         assert np.abs(_reproject(X, R0, t0, K) - _reproject(X, R1, t1, K)).max() < 1e-3
+
+
+def _cv2_pnp_f64(cv2, X, uv, K):
+    _, R_exp, t = cv2.solvePnP(np.ascontiguousarray(X), np.ascontiguousarray(uv).reshape((-1, 1, 2)), K, np.zeros((8, 1)))
+    R, _ = cv2.Rodrigues(R_exp)
+    return R, t
+
+
+@pytest.mark.skipif(_real_cv2() is None, reason="cv2 (opencv-python) is not installed here: PnP parity stays unpinned")
+def test_oracle_pnp_matches_opencv_under_noise():
+    import pnp_cases as P
+    cv2 = _real_cv2()
+    for name, d in P.golden().items():
+        for i in np.flatnonzero(d['include']):
+            R0, t0 = _cv2_pnp_f64(cv2, d['X'], d['uv'][i], P.K)
+            assert np.abs(P.reproject(d['X'], R0, t0) - P.reproject(d['X'], d['R'][i], d['t'][i])).max() < P.PARITY_PX, (name, i)
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(_real_cv2() is None, reason="cv2 (opencv-python) is not installed here: PnP parity stays unpinned")
+def test_hip_pnp_matches_opencv_under_noise():
+    import pnp_cases as P
+    from singleshotpose_amd.utils import pnp_batched
+    cv2 = _real_cv2()
+    for name, d in P.golden().items():
+        n, N = d['uv'].shape[:2]
+        Rs, ts = pnp_batched(np.broadcast_to(d['X'], (n, N, 3)), np.array(d['uv']), P.K)
+        for i in np.flatnonzero(d['include']):
+            R0, t0 = _cv2_pnp_f64(cv2, d['X'], d['uv'][i], P.K)
+            assert np.abs(P.reproject(d['X'], R0, t0) - P.reproject(d['X'], Rs[i], ts[i])).max() < P.PARITY_PX, (name, i)

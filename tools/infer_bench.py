@@ -3,6 +3,7 @@
 forward at 672x672 (valid.py's test size), decode, batched PnP, batched pose errors, RegionLoss, fused SGD, and the
 multi-object validator (eval_multi: evaluate_multi_batched against today's per-ground-truth host route).
 Prints one JSON object; numbers go to DESIGN.md section 3.  `infer_bench.py eval_multi` runs that line alone;
+`infer_bench.py pnp` the batched PnP line alone;
 `infer_bench.py adds` times ADD-S and the per-class validator."""
 import json
 import os
@@ -149,10 +150,31 @@ def adds(res):
                                                             'ground_truths': rows, 'adds_rows': nsym}
 
 
+def pnp(res):
+    """64 noise-free synthetic poses (ape-sized box, LINEMOD intrinsics) through pnp_batched, host copies included;
+    returns what the pose-error rows of main() go on with."""
+    from singleshotpose_amd import utils as U
+    rs = np.random.RandomState(0)
+    n = 64
+    half = np.array([0.038, 0.039, 0.046])
+    corners = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]) * half
+    obj = np.concatenate((np.zeros((1, 3)), corners), axis=0)
+    K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.5704, 242.0489], [0.0, 0.0, 1.0]])
+    R = np.stack([np.linalg.qr(rs.standard_normal((3, 3)))[0] for _ in range(n)])
+    R *= np.sign(np.linalg.det(R))[:, None, None]
+    t = np.stack([np.array([[rs.uniform(-.1, .1)], [rs.uniform(-.1, .1)], [rs.uniform(.6, 1.2)]]) for _ in range(n)])
+    cam = np.einsum('ij,njk->nik', K, np.einsum('nij,kj->nik', R, obj) + t)
+    uv = (cam[:, :2] / cam[:, 2:3]).transpose(0, 2, 1)
+    objs = np.broadcast_to(obj, (n, 9, 3))
+    dt = timed(lambda: U.pnp_batched(objs, uv, K), 20)
+    res['pnp_batched_64_incl_h2d_d2h'] = {'us': round(dt * 1e6, 1)}
+    return rs, half, objs, uv, K, R, t
+
+
 def main():
-    if sys.argv[1:] in (['eval_multi'], ['adds']):
+    if sys.argv[1:] in (['eval_multi'], ['adds'], ['pnp']):
         res = {}
-        (eval_multi if sys.argv[1] == 'eval_multi' else adds)(res)
+        {'eval_multi': eval_multi, 'adds': adds, 'pnp': pnp}[sys.argv[1]](res)
         print(json.dumps(res))
         return
     from singleshotpose_amd import utils as U
@@ -174,21 +196,7 @@ def main():
         res['decode_argmax_b64_21x21'] = {'us': round(dt * 1e6, 1)}
         dt = timed(lambda: U.get_region_boxes(out, 1, 9), 10)
         res['get_region_boxes_b64_21x21_incl_host_list'] = {'us': round(dt * 1e6, 1)}
-    # PnP + pose errors on synthetic poses (ape-sized box, LINEMOD intrinsics)
-    rs = np.random.RandomState(0)
-    n = 64
-    half = np.array([0.038, 0.039, 0.046])
-    corners = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]) * half
-    obj = np.concatenate((np.zeros((1, 3)), corners), axis=0)
-    K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.5704, 242.0489], [0.0, 0.0, 1.0]])
-    R = np.stack([np.linalg.qr(rs.standard_normal((3, 3)))[0] for _ in range(n)])
-    R *= np.sign(np.linalg.det(R))[:, None, None]
-    t = np.stack([np.array([[rs.uniform(-.1, .1)], [rs.uniform(-.1, .1)], [rs.uniform(.6, 1.2)]]) for _ in range(n)])
-    cam = np.einsum('ij,njk->nik', K, np.einsum('nij,kj->nik', R, obj) + t)
-    uv = (cam[:, :2] / cam[:, 2:3]).transpose(0, 2, 1)
-    objs = np.broadcast_to(obj, (n, 9, 3))
-    dt = timed(lambda: U.pnp_batched(objs, uv, K), 20)
-    res['pnp_batched_64_incl_h2d_d2h'] = {'us': round(dt * 1e6, 1)}
+    rs, half, objs, uv, K, R, t = pnp(res)
     verts = rs.uniform(-1, 1, (5841, 3)) * half          # the ape mesh has 5841 vertices
     Rg, tg = U.pnp_batched(objs, uv, K)
     dt = timed(lambda: U.pose_errors_batched(verts.T, Rg, tg, R, t, K), 20)
