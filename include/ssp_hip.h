@@ -114,6 +114,17 @@ int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int
  * zeroed by the caller (split reduction uses fp32 atomics). */
 int ssp_conv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                    int ldx, int R, void* stream);
+/* Which kernel instantiation ssp_conv_wgrad runs for these arguments under the current wgrad_variant option: a pure host
+ * function of the shape (no GPU call; works on a machine without a GPU), the one the launch itself switches on.
+ *   family*100000000 + ring_slots*10000000 + flags*1000000 + BMO*1000 + BNI
+ *   family 1 = LDS-direct loader (csrc/conv_wgrad_dma.hip), 2 = register-staged loader, 3 = the first layer's 4-channel
+ *   kernel (both csrc/conv_wgrad.hip); BMO x BNI = couts x cins of a workgroup's filter tile; ring_slots = staged pixel
+ *   chunks in the LDS; flags bit 0 = fold (Cin 32: two filter taps share a 64-column tile), bit 1 = interleaved cin blocks
+ *   (an experiment variant).  E.g. 130256128 = LDS-direct 256 x 128 on three slots, 141064064 = folded LDS-direct 64 x 64,
+ *   230032128 = register-staged 32 x 128 (the 1024 -> 20 head), 320032004 = the 4-channel kernel.
+ * 0: the launch refuses these arguments (R, Cin % 4, leading dimensions, pixel count; no pixel or no filter).  The pixel
+ * split is not part of the code: it depends on the device's occupancy and is chosen inside the launch. */
+int ssp_conv_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R);
 /* The same filter gradient of a 3x3 layer (Cin, Cout >= 64 and % 16 == 0) evaluated in the Winograd F(tile x tile, 3x3)
  * domain, tile = 2 or 4 (csrc/conv_wino.hip): dw += the direct result to ~1e-6 (tile 2) / ~4e-6 (tile 4: the direct
  * kernel's own rounding level) of its range with 16/36 / 36/144 of the multiplies.  dw must be 16-byte

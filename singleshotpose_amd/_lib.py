@@ -41,6 +41,7 @@ _SIGS = {
     "ssp_conv_dgrad_bnbwd": [P, P, P, I, I, I, I, I, I, I, I, I, P, L, P, I, P, P, P, P, F, P, I, P],
     "ssp_bn_act_bwd_partials": [P, I, P, I, P, I, P, P, P, P, I, I, I, I, F, I, P, I, I, P, P, P, P, P],
     "ssp_conv_wgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
+    "ssp_conv_wgrad_route": [I, I, I, I, I, I, I, I],
     "ssp_conv_wgrad_wino": [P, P, P, I, I, I, I, I, I, I, P, L, P],
     "ssp_conv_wgrad_wino_workspace_floats": [I, I, I, I, I],
     "ssp_conv_wgrad_wino_t": [P, P, P, I, I, I, I, I, I, I, I, P, L, P],

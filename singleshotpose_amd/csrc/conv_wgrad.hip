@@ -366,31 +366,37 @@ int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int
   a.dy = dy; a.x = x; a.dw = dw;
   a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = B * H * W;
   SspProfScope prof(SSP_PROF_CONV_WGRAD, stream, 2.0 * (double)a.M * Cout * (double)(R * R * Cin));
-  if (ssp_option(SSP_OPT_WGRAD_VARIANT) != 2) {   // LDS-direct loader for tiles with >= 64 couts and >= 64 cins
+  // one host function picks the instantiation (ssp_wgrad_route, conv_wgrad_dma.hip); the pixel split stays with the launchers
+  const int route = ssp_wgrad_route(B, H, W, Cin, Cout, lddy, ldx, R, 0, ssp_option(SSP_OPT_WGRAD_VARIANT));
+  if (route / 100000000 == SSP_WGRAD_LDS) {   // LDS-direct loader for tiles with >= 64 couts and >= 64 cins
     const int r = ssp_conv_wgrad_dma_try(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, stream);
     if (r != 0) return r < 0 ? r : SSP_OK;
+    ssp_set_error("wgrad: the LDS-direct launcher declined route %d", route);
+    return SSP_ERR_ARG;
   }
-  if (Cin == 4 && Cout == 32 && R == 3 && ldx == 4 && ssp_option(SSP_OPT_WGRAD_VARIANT) != 1) {
-    // ~8 workgroups per CU, each a multiple of 64 pixels
-    int64_t chunk = (a.M + 2047) / 2048;
-    chunk = (chunk + 63) / 64 * 64;
-    a.chunk_m = (int)chunk;
-    a.nsplit = ssp_cdiv(a.M, chunk);
-    hipLaunchKernelGGL(conv_wgrad_c4_kernel, dim3(a.nsplit), dim3(256), 0, stream, a);
-    SSP_CHECK_LAUNCH("conv_wgrad_c4");
-    return SSP_OK;
+  switch (route) {
+    case ssp_wgrad_code(SSP_WGRAD_C4, 2, false, false, 32, 4): {
+      // ~8 workgroups per CU, each a multiple of 64 pixels
+      int64_t chunk = (a.M + 2047) / 2048;
+      chunk = (chunk + 63) / 64 * 64;
+      a.chunk_m = (int)chunk;
+      a.nsplit = ssp_cdiv(a.M, chunk);
+      hipLaunchKernelGGL(conv_wgrad_c4_kernel, dim3(a.nsplit), dim3(256), 0, stream, a);
+      SSP_CHECK_LAUNCH("conv_wgrad_c4");
+      return SSP_OK;
+    }
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 128): return launch_wgrad<128, 128, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 64): return launch_wgrad<128, 64, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 32): return launch_wgrad<128, 32, 4, 1, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 128): return launch_wgrad<64, 128, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 64): return launch_wgrad<64, 64, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 32): return launch_wgrad<64, 32, 2, 1, 2>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 128): return launch_wgrad<32, 128, 1, 4, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 64): return launch_wgrad<32, 64, 1, 2, 2>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 32): return launch_wgrad<32, 32, 1, 1, 4>(a, stream);
   }
-  const int bo = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
-  const int bi = Cin >= 128 ? 128 : (Cin >= 64 ? 64 : 32);
-  if (bo == 128 && bi == 128) return launch_wgrad<128, 128, 2, 2, 1>(a, stream);
-  if (bo == 128 && bi == 64) return launch_wgrad<128, 64, 2, 2, 1>(a, stream);
-  if (bo == 128 && bi == 32) return launch_wgrad<128, 32, 4, 1, 1>(a, stream);
-  if (bo == 64 && bi == 128) return launch_wgrad<64, 128, 2, 2, 1>(a, stream);
-  if (bo == 64 && bi == 64) return launch_wgrad<64, 64, 2, 2, 1>(a, stream);
-  if (bo == 64 && bi == 32) return launch_wgrad<64, 32, 2, 1, 2>(a, stream);
-  if (bo == 32 && bi == 128) return launch_wgrad<32, 128, 1, 4, 1>(a, stream);
-  if (bo == 32 && bi == 64) return launch_wgrad<32, 64, 1, 2, 2>(a, stream);
-  return launch_wgrad<32, 32, 1, 1, 4>(a, stream);
+  ssp_set_error("wgrad: no instantiation for route %d", route);
+  return SSP_ERR_ARG;
 }
 
 

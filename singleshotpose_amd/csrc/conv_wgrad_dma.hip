@@ -510,15 +510,51 @@ static int wgrad_est_split(int64_t M, int batch, int Cout, int Cin, int bmo, int
   return (int)best_sp;
 }
 
+// The choice of instantiation, for both filter-gradient launchers (declared in ssp_common.h).
+int ssp_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int batch, int variant) {
+  // what ssp_conv_wgrad_launch refuses (its pointer-alignment test aside), and shapes without a pixel or a filter
+  if (!(R == 1 || R == 3) || B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+  if (Cin <= 0 || Cin % 4 != 0 || ldx % 4 != 0 || ldx < Cin || lddy % 4 != 0 || lddy < Cout) return 0;
+  const int64_t M = (int64_t)B * H * W;
+  if (M >= (1ll << 31)) return 0;
+  // LDS-direct loader: tiles with >= 64 couts and >= 64 cins (Cin 32: two taps fold into one 64-column tile); the
+  // per-lane pixel walker advances 16 pixels with at most two row wraps (W >= 8); 32-bit lane offsets: 16 staged rows of
+  // the widest operand, and the whole dY range of a workgroup
+  const bool lds = Cout >= 64 && (Cin >= 64 || (Cin == 32 && R == 3)) && W >= 8 &&
+                   (int64_t)16 * lddy * 4 < (1ll << 31) && (int64_t)(2 * W + 18) * ldx * 4 < (1ll << 31);
+  if (lds && (variant != 2 || batch > 1)) {      // wgrad_variant 2: register-staged kernels only (direct launches)
+    if (Cin == 32) return ssp_wgrad_code(SSP_WGRAD_LDS, 4, true, false, Cout >= 128 ? 128 : 64, 64);
+    // 256-cout tiles (128x64 per wave) on a 3-slot ring, two workgroups per CU: fewer LDS reads, DMA pieces and border
+    // walks per MFMA than 128x128, and - what decides it inside the training step, where the data-gradient kernel runs
+    // concurrently on the other stream - two fat workgroups per CU leave that kernel room (whole-step A/B on one box:
+    // 50.8 ms against 52.3 ms for 128x128 tiles at three per CU, although the stand-alone launch times are equal)
+    if (Cout >= 256 && Cin >= 128 && variant != 8 &&
+        !(batch > 1 && wgrad_est_split(M, batch, Cout, Cin, 128, 768) < wgrad_est_split(M, batch, Cout, Cin, 256, 512)))
+      return ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, false, 256, 128);
+    if (Cout >= 128 && Cin >= 128 && variant == 6) return ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, true, 128, 128);    // experiment
+    if (Cout >= 128 && Cin >= 128 && variant == 3) return ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 128, 128);   // experiment
+    // 3-slot ring: 48 KB of LDS, three workgroups per CU (measured +3..6 % over the 4-slot ring at two per CU)
+    if (Cout >= 128 && Cin >= 128) return ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, false, 128, 128);
+    if (Cout >= 128) return ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 128, 64);
+    if (Cin >= 128) return ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 64, 128);
+    return ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 64, 64);
+  }
+  if (batch > 1) return 0;
+  // first layer (RGB + zero pad): the nine taps folded into the column dimension (conv_wgrad.hip), a 2-slot ring
+  if (Cin == 4 && Cout == 32 && R == 3 && ldx == 4 && variant != 1) return ssp_wgrad_code(SSP_WGRAD_C4, 2, false, false, 32, 4);
+  // register-staged kernels (conv_wgrad.hip; 3-slot ring): one instantiation per (cout tile, cin tile)
+  const int bo = Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
+  const int bi = Cin >= 128 ? 128 : (Cin >= 64 ? 64 : 32);
+  return ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, bo, bi);
+}
+
 // returns 1 when the shape is handled here (launched), 0 when the caller should use conv_wgrad.hip, < 0 on error
 int ssp_conv_wgrad_dma_try(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                            int ldx, int R, hipStream_t stream, int batch, int64_t batch_dy, int64_t batch_x,
                            int64_t batch_dw, int overwrite) {
-  if (Cout < 64 || (Cin < 64 && !(Cin == 32 && R == 3))) return 0;   // Cin 32: two taps fold into one 64-column tile
-  if (W < 8) return 0;   // the per-lane pixel walker advances 16 pixels with at most two row wraps
+  const int route = ssp_wgrad_route(B, H, W, Cin, Cout, lddy, ldx, R, batch, ssp_option(SSP_OPT_WGRAD_VARIANT));
+  if (route / 100000000 != SSP_WGRAD_LDS) return 0;
   const int64_t M = (int64_t)B * H * W;
-  // 32-bit lane offsets: 16 staged rows of the widest operand, and the whole dY range of a workgroup
-  if ((int64_t)16 * lddy * 4 >= (1ll << 31) || (int64_t)(2 * W + 18) * ldx * 4 >= (1ll << 31)) return 0;
   WgradArgs a;
   a.dy = dy; a.x = x; a.dw = dw;
   a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = (int)M;
@@ -531,20 +567,19 @@ int ssp_conv_wgrad_dma_try(const float* dy, const float* x, float* dw, int B, in
     a.zero_bytes = (size_t)(batch > 1 ? batch : 1) * (size_t)(batch > 1 ? batch_dw : (int64_t)Cout * R * R * Cin) * 4;
   }
   int rc;
-  const int wv = ssp_option(SSP_OPT_WGRAD_VARIANT);
-  if (Cin == 32) rc = (Cout >= 128) ? launch_wgrad_dma<128, 64, 4, true>(a, stream) : launch_wgrad_dma<64, 64, 4, true>(a, stream);
-  // 256-cout tiles (128x64 per wave) on a 3-slot ring, two workgroups per CU: fewer LDS reads, DMA pieces and border
-  // walks per MFMA than 128x128, and - what decides it inside the training step, where the data-gradient kernel runs
-  // concurrently on the other stream - two fat workgroups per CU leave that kernel room (whole-step A/B on one box:
-  // 50.8 ms against 52.3 ms for 128x128 tiles at three per CU, although the stand-alone launch times are equal)
-  else if (Cout >= 256 && Cin >= 128 && wv != 8 && !(batch > 1 && wgrad_est_split(M, batch, Cout, Cin, 128, 768) < wgrad_est_split(M, batch, Cout, Cin, 256, 512)))
-    rc = launch_wgrad_dma<256, 128, 3>(a, stream);
-  else if (Cout >= 128 && Cin >= 128 && wv == 6) rc = launch_wgrad_dma<128, 128, 3, false, true>(a, stream);   // experiment
-  else if (Cout >= 128 && Cin >= 128 && wv == 3) rc = launch_wgrad_dma<128, 128, 4>(a, stream);           // experiment
-  // 3-slot ring: 48 KB of LDS, three workgroups per CU (measured +3..6 % over the 4-slot ring at two per CU)
-  else if (Cout >= 128 && Cin >= 128) rc = launch_wgrad_dma<128, 128, 3>(a, stream);
-  else if (Cout >= 128) rc = launch_wgrad_dma<128, 64>(a, stream);
-  else if (Cin >= 128) rc = launch_wgrad_dma<64, 128>(a, stream);
-  else rc = launch_wgrad_dma<64, 64>(a, stream);
+  switch (route) {
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, true, false, 128, 64): rc = launch_wgrad_dma<128, 64, 4, true>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, true, false, 64, 64): rc = launch_wgrad_dma<64, 64, 4, true>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, false, 256, 128): rc = launch_wgrad_dma<256, 128, 3>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, true, 128, 128): rc = launch_wgrad_dma<128, 128, 3, false, true>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 128, 128): rc = launch_wgrad_dma<128, 128, 4>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 3, false, false, 128, 128): rc = launch_wgrad_dma<128, 128, 3>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 128, 64): rc = launch_wgrad_dma<128, 64>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 64, 128): rc = launch_wgrad_dma<64, 128>(a, stream); break;
+    case ssp_wgrad_code(SSP_WGRAD_LDS, 4, false, false, 64, 64): rc = launch_wgrad_dma<64, 64>(a, stream); break;
+    default:
+      ssp_set_error("conv_wgrad_dma: no instantiation for route %d", route);
+      return SSP_ERR_ARG;
+  }
   return rc == SSP_OK ? 1 : rc;
 }

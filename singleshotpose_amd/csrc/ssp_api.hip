@@ -315,6 +315,9 @@ int ssp_conv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int
   return ssp_conv_wgrad_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, (hipStream_t)stream);
 }
 
+int ssp_conv_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R) {
+  return ssp_wgrad_route(B, H, W, Cin, Cout, lddy, ldx, R, 0, ssp_option(SSP_OPT_WGRAD_VARIANT));
+}
 int64_t ssp_conv_wgrad_wino_workspace_floats_t(int B, int H, int W, int Cin, int Cout, int tile) {
   return ssp_conv_wgrad_wino_ws_floats(B, H, W, Cin, Cout, tile);
 }

@@ -69,6 +69,17 @@ struct SspProfScope {
 enum SspOption { SSP_OPT_IGEMM_XCD = 0, SSP_OPT_IGEMM_VARIANT = 1, SSP_OPT_WGRAD_VARIANT = 2, SSP_OPT_IGEMM_PLAN = 3, SSP_OPT_WGRAD_SPLIT = 4, SSP_OPT_WINO_VARIANT = 5, SSP_OPT_ACC_CHUNK = 6, SSP_OPT_COUNT = 7 };
 int ssp_option(int which);
 
+// Which kernel instantiation a direct filter-gradient launch of that shape runs (conv_wgrad_dma.hip): a pure host
+// function of the launch shape and the wgrad_variant knob - both launchers switch on its result, and
+// ssp_conv_wgrad_route (include/ssp_hip.h, where the code is documented) hands it to callers.  0 = the launch refuses
+// these arguments.  batch > 1: a batched launch (the planes of a Winograd filter gradient), which only the LDS-direct
+// family serves - 0 when that family declines the shape.
+enum { SSP_WGRAD_LDS = 1, SSP_WGRAD_REG = 2, SSP_WGRAD_C4 = 3 };
+constexpr int ssp_wgrad_code(int family, int nslot, bool fold, bool bvec, int bmo, int bni) {
+  return family * 100000000 + nslot * 10000000 + ((fold ? 1 : 0) + (bvec ? 2 : 0)) * 1000000 + bmo * 1000 + bni;
+}
+int ssp_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int batch, int variant);
+
 // Per-device cache of one kernel instantiation's dynamic-LDS reservation and chip-wide resident-workgroup count
 // (the only mutable state the library keeps besides the experiment knobs): filled under a mutex, one entry per HIP
 // device so that several devices driven from one process each get their hipFuncSetAttribute call.

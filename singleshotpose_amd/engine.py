@@ -29,6 +29,15 @@ WINO4 = 8000000      # ... and WINO4 + the same: F(4x4, 3x3)
 WGRAD_FUSED = 12     # `tile` value of ssp_conv_wgrad_wino_t: F(2x2) filter gradient with both transforms on the chip
 WINOF = 7000001      # F(2x2, 3x3) with the transform domain kept on the chip (csrc/conv_wino_fused.hip): one persistent launch,
                      # no workspace; same transformed filters, same arithmetic (and error family) as a WINO plan
+# Direct plan codes Plan._autotune times (include/ssp_hip.h: tail*100000 + tile_rows*100 + ksplit*10 + ring_slots): tile
+# rows x split-K x ring depth; 2xxxxx / 3xxxxx / 4xxxxx = hybrid launches (whole resident waves un-split, the tiles of the
+# last partial wave split 2 / 3 / 4 ways over K)
+IGEMM_CANDS = (12813, 12814, 6414, 6413, 12824, 12834, 306413, 306414, 312813, 312814, 206413, 212814,
+               12823, 6423, 6424, 206414, 212813, 406413, 406414, 412813)
+# ring depth 8 = the latency form of the kernel (one workgroup per CU, 7 chunks in flight)
+IGEMM_LATENCY_CANDS = (6418, 12818, 6428, 12828, 6438)
+# GEMM tilings tried under a Winograd base (WINO / WINO4 + code)
+WINO_GEMM_CANDS = (6413, 6414, 12813, 12814)
 
 
 def _tune_tag():
@@ -1027,11 +1036,10 @@ class Plan(object):
         n_known = len(_TUNE_CACHE)
         # tile rows x split-K x ring depth; 3xxxxx / 2xxxxx = hybrid launches (whole resident waves un-split, the tiles of
         # the last partial wave split 3 / 2 ways over K)
-        cands = (12813, 12814, 6414, 6413, 12824, 12834, 306413, 306414, 312813, 312814, 206413, 212814,
-                 12823, 6423, 6424, 206414, 212813, 406413, 406414, 412813)
+        cands = IGEMM_CANDS
         # ring depth 8 = the latency form of the kernel (one workgroup per CU, 7 chunks in flight): only worth timing on
         # grids that cannot give a CU several workgroups anyway (small-batch inference)
-        lat = (6418, 12818, 6428, 12828, 6438)
+        lat = IGEMM_LATENCY_CANDS
         elig = [cs for cs in self.convs.values() if cs.cinp % 16 == 0]
         if not elig:
             return
@@ -1041,7 +1049,7 @@ class Plan(object):
         # profiles/r03_step_ab_winograd.txt).  SSP_WINOGRAD=0 turns them off, SSP_WINO_MIN_CHANNELS moves the threshold.
         # F(4x4, 3x3) candidates (WINO4): 36/144 of the multiplies and 2.25 instead of 4 transform floats per pixel, so they
         # are timed from 64 channels up (SSP_WINO_TILES=2 or =4 restricts the tile sizes tried).
-        gemm_cands = (6413, 6414, 12813, 12814)
+        gemm_cands = WINO_GEMM_CANDS
         wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
         wino_min = int(os.environ.get('SSP_WINO_MIN_CHANNELS', '128'))
         wino_tiles = tuple(int(t) for t in os.environ.get('SSP_WINO_TILES', '2,4').split(',') if t)

@@ -102,16 +102,17 @@ def test_conv_fwd(B, H, W, Cin, Cout, R, xin, xout, bias):
         np.testing.assert_allclose(rvd.cpu().numpy(), rv_ref.numpy(), rtol=1e-4, atol=1e-5)
 
 
+# (filter-gradient kernel of each case as ssp_conv_wgrad_route names it; tests/test_gpu_conv_exact.py asserts the route)
 GRAD_CASES = [
-    (2, 13, 13, 64, 128, 3),
-    (1, 20, 24, 3, 32, 3),      # first layer (wgrad only)
-    (2, 10, 12, 128, 64, 1),
-    (3, 7, 9, 32, 20, 1),       # head: dY with 20 channels
-    (2, 12, 12, 32, 64, 3),     # 64x32 wgrad tile with in-workgroup K split
-    (4, 13, 13, 256, 256, 3),
-    (2, 26, 26, 512, 64, 1),
-    (64, 13, 13, 64, 512, 3),   # dgrad/wgrad at the 13x13 benchmark grid (split-K dgrad)
-    (4, 3, 3, 64, 64, 3),       # tiny maps: fewer pixels than one staged chunk, W < 8
+    (2, 13, 13, 64, 128, 3),    # LDS-direct 128x64 wgrad tile
+    (1, 20, 24, 3, 32, 3),      # first layer (wgrad only): the 4-channel kernel
+    (2, 10, 12, 128, 64, 1),    # LDS-direct 64x128
+    (3, 7, 9, 32, 20, 1),       # head: dY with 20 channels; register-staged 32x32 wgrad tile with in-workgroup K split
+    (2, 12, 12, 32, 64, 3),     # Cin 32: two filter taps folded into one 64-column tile of the LDS-direct kernel (64 couts)
+    (4, 13, 13, 256, 256, 3),   # LDS-direct 256x128 on a 3-slot ring
+    (2, 26, 26, 512, 64, 1),    # LDS-direct 64x128
+    (64, 13, 13, 64, 512, 3),   # dgrad/wgrad at the 13x13 benchmark grid (split-K dgrad); LDS-direct 128x64
+    (4, 3, 3, 64, 64, 3),       # tiny maps: fewer pixels than one staged chunk, W < 8: register-staged 64x64
     (3, 9, 11, 128, 64, 3),     # W < 16: the LDS-direct wgrad loader wraps image rows twice per chunk
     (1, 9, 11, 32, 128, 3),     # Cin 32: two filter taps folded into one 64-column wgrad tile (128-cout tile)
     (2, 16, 20, 32, 64, 3),     # same, 64-cout tile (layer 2 of yolo-pose.cfg)
