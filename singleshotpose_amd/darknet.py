@@ -154,8 +154,13 @@ class Darknet(nn.Module):
                 if len(layers) == 1:
                     prev_filters = out_filters[layers[0]]
                 elif len(layers) == 2:
-                    assert layers[0] == ind - 1
+                    if layers[0] != ind - 1:
+                        raise NotImplementedError("block %d (route): the first of two layers must be the previous layer "
+                                                  "(darknet.py:206), got %d" % (ind, layers[0]))
                     prev_filters = out_filters[layers[0]] + out_filters[layers[1]]
+                else:
+                    raise NotImplementedError("block %d (route): %d layers (the reference's darknet.py:99-106 handles one or "
+                                              "two)" % (ind, len(layers)))
                 out_filters.append(prev_filters)
                 models.append(EmptyModule())
             elif t == 'shortcut':

@@ -366,8 +366,12 @@ class Plan(object):
                 cs.cin = in_c if cs.first else prev.C
                 cs.cinp = _pad4(cs.cin)
                 cs.cout = c
+                if conv.weight.shape[1] != cs.cin:
+                    raise NotImplementedError("block %d (%s): its parameter takes %d input channels but the map it is given "
+                                              "has %d" % (ind, t, conv.weight.shape[1], cs.cin))
                 if prev.ld < cs.cinp:
-                    raise NotImplementedError("conv input with a channel count that is not a multiple of 4")
+                    raise NotImplementedError("block %d (%s): its %d-channel input map has a row stride of %d floats, narrower "
+                                              "than the padded channel count %d" % (ind, t, cs.cin, prev.ld, cs.cinp))
                 cs.H, cs.W = prev.H, prev.W
                 cs.coutp = _pad4(c)
                 cs.conv, cs.bnm = conv, bnm
@@ -408,6 +412,10 @@ class Plan(object):
                 # out; the cfg's size is ignored, as in the reference
                 if s != 1 and (k != 2 or s != 2):
                     raise NotImplementedError("maxpool size=%d stride=%d (MaxPoolStride1, darknet.py:8-14) is not instantiated by the pose cfgs; not built" % (k, s))
+                if s == 2 and (prev.H % 2 or prev.W % 2):
+                    # (a pool fused into its BatchNorm block never gets here; the fusion itself needs an even map)
+                    raise NotImplementedError("block %d (maxpool): a standalone 2x2/2 max-pool of a %d x %d map "
+                                              "(ssp_maxpool_fwd needs even H and W)" % (ind, prev.W, prev.H))
                 op = _Op('maxpool_s1' if s == 1 else 'maxpool', ind, [prev],
                          _Act(torch.empty(B * h * w * prev.ld, **f32), 0, c, h, w, prev.ld))
             elif t == 'reorg':
@@ -415,6 +423,9 @@ class Plan(object):
                     raise NotImplementedError("reorg stride != 2")
                 if prev.C % 4:
                     raise NotImplementedError("reorg of a %d-channel map (ssp_reorg needs a multiple of 4)" % prev.C)
+                if prev.H % 2 or prev.W % 2:
+                    raise NotImplementedError("block %d (reorg): reorg of a %d x %d map (ssp_reorg needs even H and W)"
+                                              % (ind, prev.W, prev.H))
                 op = _Op('reorg', ind, [prev], _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c))
             elif t == 'shortcut':
                 f = resolve_layers(block['from'], ind)[0]
@@ -438,12 +449,22 @@ class Plan(object):
                 op = _Op('softmax', ind, [prev], out)
             elif t == 'route':
                 layers = resolve_layers(block['layers'], ind)
+                if len(layers) > 2:
+                    raise NotImplementedError("block %d (route): %d layers (the reference's darknet.py:99-106 handles one "
+                                              "or two)" % (ind, len(layers)))
+                if len(layers) == 2 and layers[0] != ind - 1:
+                    raise NotImplementedError("block %d (route): the first of two layers must be the previous layer "
+                                              "(darknet.py:206), got %d" % (ind, layers[0]))
                 srcs = [self.acts[l] for l in layers]
                 if any(s is None for s in srcs):
                     raise RuntimeError("route to a layer whose output was fused away")
                 if len(layers) == 1:
                     op = _Op('alias', ind, srcs, srcs[0])
                 else:
+                    for l, s in zip(layers, srcs):
+                        if s.C % 4:
+                            raise NotImplementedError("block %d (route): concatenates layer %d with %d channels "
+                                                      "(ssp_copy_channels needs multiples of 4)" % (ind, l, s.C))
                     op = _Op('concat', ind, srcs, _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c, srcs[0].flat))
             else:  # region / cost: not executed in forward (darknet.py:119-127)
                 self._place(ind, prev)
@@ -451,6 +472,11 @@ class Plan(object):
             self.ops.append(op)
             self._place(op.oind, op.out)
             prev = op.out
+        o = self.acts[self.last]
+        if o.ld > o.C:
+            # (the gradient of the output arrives NCHW and is laid out with ld = C by Plan.backward)
+            raise NotImplementedError("block %d (%s): the network output has %d channels, not a multiple of 4"
+                                      % (self.last, blocks[self.last + 1]['type'], o.C))
         # Filter staging buffers are allocated when first needed: channels-last parameters are used in place, so only the
         # padded first layer (or a filter a caller replaced by a plain contiguous tensor) gets a forward / gradient
         # staging copy, and the data-gradient operands (202 MB) exist only in plans that run a backward.
@@ -1618,8 +1644,6 @@ class Plan(object):
                 tuple(grad_out.shape), (B, o.C) if self.out_flat else (B, o.C, o.H, o.W)))
         g_last = self._grad_buf(self.last, o)
         call('ssp_nchw_to_nhwc', grad_out.data_ptr(), g_last.ptr, B, o.C, o.H, o.W, o.C, o.ld, st)
-        if o.ld > o.C:
-            raise NotImplementedError("network output channels must be a multiple of 4")
         if self.side_stream is None:
             self.side_stream = _side_stream(self.device)
         if not want_params:

@@ -130,6 +130,8 @@ def _grad_layout_covers(plan, model):
 
 NET = '[net]\nheight=%d\nwidth=%d\nchannels=3\n\n'
 CONV = '[convolutional]\nbatch_normalize=1\nfilters=%d\nsize=3\nstride=1\npad=1\nactivation=leaky\n\n'
+POOL = '[maxpool]\nsize=2\nstride=2\n\n'
+HEAD = '[convolutional]\nfilters=%d\nsize=1\nstride=1\npad=1\nactivation=linear\n\n'
 
 
 @pytest.mark.parametrize('body,msg', [
@@ -138,12 +140,32 @@ CONV = '[convolutional]\nbatch_normalize=1\nfilters=%d\nsize=3\nstride=1\npad=1\
     (CONV % 8 + '[connected]\noutput=16\nactivation=leaky\n\n', 'connected'),
     (CONV % 8 + CONV % 16 + '[shortcut]\nfrom=-2\nactivation=linear\n\n', 'same shape'),
     (CONV % 8 + '[convolutional]\nfilters=8\nsize=5\nstride=1\npad=1\nactivation=leaky\n\n', 'conv'),
+    # what a launch would decline, or worse, is declined when the plan is built (the bodies of tests/topology_cases.py)
+    (CONV % 8 + CONV % 8 + CONV % 8 + '[route]\nlayers=-1,-3,-1\n\n' + HEAD % 20, r'block 3 \(route\): 3 layers'),
+    (CONV % 8 + CONV % 8 + '[route]\nlayers=-2,-1\n\n' + HEAD % 8, r'block 2 \(route\): the first of two'),
+    (CONV % 18 + CONV % 6 + '[route]\nlayers=-1,-2\n\n' + HEAD % 8, r'block 2 \(route\): concatenates layer 1 with 6'),
+    ((CONV % 8 + POOL) * 3 + CONV % 8 + POOL + HEAD % 8, r'block 7 \(maxpool\): a standalone 2x2/2 max-pool of a 3 x 3'),
+    ((CONV % 8 + POOL) * 3 + CONV % 8 + '[reorg]\nstride=2\n\n' + HEAD % 8, r'block 7 \(reorg\): reorg of a 3 x 3'),
+    (CONV % 8 + HEAD % 18, r'block 1 \(convolutional\): the network output has 18'),
 ])
 def test_still_refused(tmp_path, body, msg):
     from singleshotpose_amd.darknet import Darknet
     from singleshotpose_amd.engine import Plan
     cfg = tmp_path / 'bad.cfg'
     cfg.write_text(NET % (24, 24) + body)
-    m = Darknet(str(cfg))
     with pytest.raises(NotImplementedError, match=msg):
+        m = Darknet(str(cfg))
+        Plan(m, 1, 24, 24, torch.device('cpu'))
+
+
+def test_parameter_width_is_checked_against_the_map(tmp_path):
+    """A conv whose parameter was built for another input width than the map the plan hands it (a module tree edited after
+    construction) is refused when the plan is built, not read out of bounds by its first launch."""
+    from singleshotpose_amd.darknet import Darknet
+    from singleshotpose_amd.engine import Plan
+    cfg = tmp_path / 'w.cfg'
+    cfg.write_text(NET % (24, 24) + CONV % 8 + CONV % 16 + HEAD % 8)
+    m = Darknet(str(cfg))
+    m.models[1][0] = torch.nn.Conv2d(4, 16, 3, 1, 1, bias=False)
+    with pytest.raises(NotImplementedError, match=r'block 1 \(convolutional\): its parameter takes 4 input channels'):
         Plan(m, 1, 24, 24, torch.device('cpu'))

@@ -1,7 +1,6 @@
 """Gradient of the network input, dL/dx (x.requires_grad_(True)): the fused first-block kernel ssp_first_bwd_dgrad through
 the C ABI against float64 autograd on the CPU, and whole networks against the CPU oracle - training and eval mode, the
 input-only backward (every parameter frozen), first blocks that are not a conv, dtypes and resolutions."""
-import copy
 import os
 
 import numpy as np
@@ -10,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import GOLD, ROOT, clone_state, load_state_into, make_targets, rel_err
+from topology_cases import ref_generic as _ref_generic
 
 pytestmark = pytest.mark.gpu
 TOL = 3e-4
@@ -174,48 +174,6 @@ def test_network_input_grad_region_loss():
     r = region_loss_ref(y.detach().float(), tgt, 20)
     y.backward(torch.as_tensor(r['grad']).double())
     assert rel_err(xg.grad.cpu().numpy(), xr.grad.numpy()) < TOL
-
-
-def _ref_generic(model, x, training):
-    """CPU float64 forward of a cfg with shortcut / stride-1 maxpool / avgpool / softmax / connected blocks, on a copy of
-    the module tree (darknet.py's forward, the reference's block semantics)."""
-    from oracle.darknet_ref import reorg_ref
-    from singleshotpose_amd.cfg import resolve_layers
-    mods = copy.deepcopy(model.models).cpu().double()
-    mods.train(training)
-    outputs = {}
-    for ind, b in enumerate(model.blocks[1:]):
-        t = b['type']
-        if t == 'convolutional':
-            x = mods[ind](x)
-        elif t == 'maxpool':
-            s = int(b['stride'])
-            x = F.max_pool2d(x, int(b['size']), s) if s > 1 else F.max_pool2d(F.pad(x, (0, 1, 0, 1), mode='replicate'), 2, 1)
-        elif t == 'avgpool':
-            x = x.mean(dim=(2, 3))
-        elif t == 'softmax':
-            x = F.softmax(x, 1)
-        elif t == 'connected':
-            m = mods[ind]
-            lin = m[0] if isinstance(m, torch.nn.Sequential) else m
-            x = F.linear(x.view(x.size(0), -1), lin.weight, lin.bias)
-            if isinstance(m, torch.nn.Sequential):
-                x = F.leaky_relu(x, 0.1) if isinstance(m[1], torch.nn.LeakyReLU) else F.relu(x)
-        elif t == 'reorg':
-            x = reorg_ref(x, int(b['stride']))
-        elif t == 'route':
-            ls = resolve_layers(b['layers'], ind)
-            x = outputs[ls[0]] if len(ls) == 1 else torch.cat([outputs[l] for l in ls], 1)
-        elif t == 'shortcut':
-            x = outputs[resolve_layers(b['from'], ind)[0]] + outputs[ind - 1]
-            if b['activation'] == 'leaky':
-                x = F.leaky_relu(x, 0.1)
-            elif b['activation'] == 'relu':
-                x = F.relu(x)
-        elif t in ('region', 'cost'):
-            continue
-        outputs[ind] = x
-    return x
 
 
 @pytest.mark.parametrize('cfg,B,H,W', [('generic-pose.cfg', 2, 80, 80), ('generic-cls.cfg', 4, 64, 64)])
