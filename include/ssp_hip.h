@@ -178,6 +178,12 @@ int ssp_bn_act_bwd_partials(const float* x, int ldx, const float* g, int ldg, fl
                             const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W,
                             float slope, int training, float* partial, int npartial, int zero_after, float* dgamma,
                             float* dbeta, float* c1, float* c2, void* stream);
+/* a BatchNorm block in inference mode whose gamma / beta want no gradient is the affine map leaky(scale*x + shift)
+ * [+ max-pool]: its backward is the apply pass alone, dx (may alias x) = scale * leaky'(.) * pool-scatter(g); no
+ * reduction, no finalize.  scale / shift / mean / invstd from ssp_bn_eval_prepare; shapes and limits as ssp_bn_act_bwd. */
+int ssp_bn_act_bwd_affine(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
+                          const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W, int pool,
+                          float slope, void* stream);
 /* just the fp64 finalize of `npartial` rows of (sum dy, sum dy * xhat) pairs -> dgamma, dbeta, c1 = mean(dy),
  * c2 = mean(dy * xhat) over npix pixels (c1 = c2 = 0 when training == 0) */
 int ssp_bn_bwd_finalize(float* partial, int npartial, int C, int64_t npix, int training, int zero_after, float* dgamma,
@@ -230,6 +236,21 @@ int ssp_first_bwd_dgrad(const float* x, const float* wt, const float* g, int ldg
  * All three pointers 16-byte aligned. */
 int ssp_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
                  float dampening, float weight_decay, int nesterov, int first_step, void* stream);
+#define SSP_SGD_MAX_TUPLES 16
+/* The same update over a TABLE of segments in one launch (parameter groups with different hyper-parameters, an optimizer
+ * that holds part of a model): segment s is table[s] = {param offset, grad offset, momentum offset, length, tuple index}
+ * (five int64, offsets and lengths in floats; offsets multiples of 4, lengths arbitrary, nseg >= 1), tuple t is
+ * hyper[t] = {lr, momentum, dampening, weight_decay, nesterov (0 / 1), first_step (0 / 1)} (six floats, at most
+ * SSP_SGD_MAX_TUPLES = 16 of them: they travel by value with the launch, so a changed lr needs no upload).
+ * Every element is updated exactly as by ssp_sgd_step on its segment (bit-identical).  table_dev is the device-resident
+ * table the kernel reads, table_host the caller's host copy of the same nseg rows: before anything is launched every row
+ * is checked against the three buffer lengths (param_floats, grad_floats, momentum_floats; momentum_buf may be NULL with
+ * momentum_floats = 0 when no tuple has momentum) - an offset that is negative, misaligned or, with its length, past the
+ * end of a buffer, a length < 1, a tuple index outside [0, ntuple) or a bad tuple is SSP_ERR_ARG and nothing runs.
+ * Segments must not overlap in param / momentum_buf (not checked).  All pointers 16-byte aligned. */
+int ssp_sgd_step_table(float* param, const float* grad, float* momentum_buf, int64_t param_floats, int64_t grad_floats,
+                       int64_t momentum_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
+                       const float* hyper, int ntuple, void* stream);
 
 /* ---- layout / index kernels -------------------------------------------------------------------------------- */
 int ssp_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* stream);

@@ -51,6 +51,7 @@ _SIGS = {
     "ssp_bn_act_fwd": [P, I, P, I, P, P, I, I, I, I, I, F, P],
     "ssp_bn_bwd_blocks": [],
     "ssp_bn_act_bwd": [P, I, P, I, P, I, P, P, P, P, I, I, I, I, I, F, I, P, P, P, P, P, P],
+    "ssp_bn_act_bwd_affine": [P, I, P, I, P, I, P, P, P, P, I, I, I, I, I, F, P],
     "ssp_bn_bwd_finalize": [P, I, I, L, I, I, P, P, P, P, P],
     "ssp_first_tile_pixels": [],
     "ssp_first_groups": [I, I, I],
@@ -69,6 +70,7 @@ _SIGS = {
     "ssp_adds_workspace_doubles": [I, I],
     "ssp_adds_errors": [P, P, P, I, I, P, P, I, P, P, L, P],
     "ssp_sgd_step": [P, P, P, L, F, F, F, F, I, I, P],
+    "ssp_sgd_step_table": [P, P, P, L, L, L, P, P, I, P, I, P],
     "ssp_nchw_to_nhwc": [P, P, I, I, I, I, I, I, P],
     "ssp_nhwc_to_nchw": [P, P, I, I, I, I, I, P],
     "ssp_u8hwc_to_nhwc": [P, P, I, I, I, I, I, I, P],

@@ -443,6 +443,27 @@ int ssp_bn_act_bwd_launch(const float* x, int ldx, const float* g, int ldg, floa
   return SSP_OK;
 }
 
+// BatchNorm in inference mode with gamma and beta frozen: the block is leaky(scale * x + shift) [+ max-pool] with constant
+// scale / shift, and its backward is the apply pass alone (dx = scale * dy, c1 = c2 = 0) - no reduction, no finalize.
+int ssp_bn_act_bwd_affine_launch(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
+                                 const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W,
+                                 int pool, float slope, hipStream_t stream) {
+  SSP_CHECK_ARG(C % 4 == 0 && C > 0 && ldx % 4 == 0 && ldg % 4 == 0 && lddx % 4 == 0,
+                "bn_act_bwd_affine: C and strides must be multiples of 4");
+  SSP_CHECK_ARG(ldx >= C && ldg >= C && lddx >= C && B > 0 && H > 0 && W > 0, "bn_act_bwd_affine: bad sizes");
+  SSP_CHECK_ARG(!pool || (H % 2 == 0 && W % 2 == 0), "bn_act_bwd_affine: pooled maps need even H, W");
+  SSP_CHECK_ARG(x != nullptr && g != nullptr && dx != nullptr && scale != nullptr && shift != nullptr && mean != nullptr &&
+                invstd != nullptr, "bn_act_bwd_affine: null operand");
+  const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
+  const int64_t npix = (int64_t)B * Ho * Wo;
+  SspProfScope prof(SSP_PROF_BN_ACT, stream, 4.0 * C * (2.0 * (double)B * H * W + (double)npix));
+  // (c1 / c2 are read and multiplied by kscale = 0: any finite per-channel vectors do - scale and shift are at hand)
+  hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(elem_grid(npix * (C / 4))), dim3(256), 0, stream, x, ldx, g, ldg, dx,
+                     lddx, scale, shift, mean, invstd, scale, shift, 0.f, C, B, H, W, pool, slope);
+  SSP_CHECK_LAUNCH("bn_act_bwd_affine");
+  return SSP_OK;
+}
+
 // The two reductions were already done by the producing data-gradient launch (ssp_conv_dgrad_bnbwd: one (sum dy,
 // sum dy * xhat) pair per M tile and channel): fp64 finalize over the tiles, then the apply pass.  Un-pooled blocks only.
 int ssp_bn_act_bwd_partials_launch(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx,

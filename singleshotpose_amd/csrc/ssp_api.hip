@@ -37,6 +37,9 @@ int ssp_bn_act_bwd_partials_launch(const float* x, int ldx, const float* g, int 
                                    int C, int B, int H, int W, float slope, int training, float* partial,
                                    int npartial, int zero_after, float* dgamma, float* dbeta, float* c1, float* c2,
                                    hipStream_t stream);
+int ssp_bn_act_bwd_affine_launch(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
+                                 const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W,
+                                 int pool, float slope, hipStream_t stream);
 int ssp_bn_bwd_finalize_launch(float* partial, int npartial, int C, int64_t npix, int training, int zero_after,
                                float* dgamma, float* dbeta, float* c1, float* c2, hipStream_t stream);
 int ssp_first_tile_pixels_impl(void);
@@ -60,6 +63,9 @@ int ssp_first_bwd_dgrad_launch(const float* x, const float* wt, const float* g, 
 int ssp_colsum_launch(const float* g, int ldg, int64_t M, int C, float* out, hipStream_t stream);
 int ssp_sgd_step_launch(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
                         float weight_decay, int nesterov, int first_step, hipStream_t stream);
+int ssp_sgd_step_table_launch(float* p, const float* g, float* m, int64_t p_floats, int64_t g_floats, int64_t m_floats,
+                              const int64_t* table_dev, const int64_t* table_host, int nseg, const float* hyper, int ntuple,
+                              hipStream_t stream);
 int ssp_nchw_to_nhwc_launch(const float* src, float* dst, int B, int C, int H, int W, int Cp, int ld, hipStream_t stream);
 int ssp_nhwc_to_nchw_launch(const float* src, float* dst, int B, int C, int H, int W, int ld, hipStream_t stream);
 int ssp_pose_errors_launch(const double* verts, int N, const double* Rt_gt, const double* Rt_pr, const double* K,
@@ -359,6 +365,12 @@ int ssp_bn_act_bwd(const float* x, int ldx, const float* g, int ldg, float* dx, 
   return ssp_bn_act_bwd_launch(x, ldx, g, ldg, dx, lddx, scale, shift, mean, invstd, C, B, H, W, pool, slope, training,
                                partial, dgamma, dbeta, c1, c2, (hipStream_t)stream);
 }
+int ssp_bn_act_bwd_affine(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
+                          const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W, int pool,
+                          float slope, void* stream) {
+  return ssp_bn_act_bwd_affine_launch(x, ldx, g, ldg, dx, lddx, scale, shift, mean, invstd, C, B, H, W, pool, slope,
+                                      (hipStream_t)stream);
+}
 int ssp_bn_bwd_blocks(void) { return ssp_bn_bwd_blocks_impl(); }
 int ssp_colsum(const float* g, int ldg, int64_t M, int C, float* out, void* stream) {
   return ssp_colsum_launch(g, ldg, M, C, out, (hipStream_t)stream);
@@ -367,6 +379,12 @@ int ssp_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n
                  float dampening, float weight_decay, int nesterov, int first_step, void* stream) {
   return ssp_sgd_step_launch(param, grad, momentum_buf, n, lr, momentum, dampening, weight_decay, nesterov, first_step,
                              (hipStream_t)stream);
+}
+int ssp_sgd_step_table(float* param, const float* grad, float* momentum_buf, int64_t param_floats, int64_t grad_floats,
+                       int64_t momentum_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
+                       const float* hyper, int ntuple, void* stream) {
+  return ssp_sgd_step_table_launch(param, grad, momentum_buf, param_floats, grad_floats, momentum_floats, table_dev,
+                                   table_host, nseg, hyper, ntuple, (hipStream_t)stream);
 }
 
 int ssp_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* stream) {

@@ -287,13 +287,16 @@ class Darknet(nn.Module):
                 raise RuntimeError("model parameters are on %s but the input is on %s - call model.cuda()" % (p.device, x.device))
         plan = self._plan(shape, x.device)
         need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        if need_grad and self.training:
-            return _DarknetFn.apply(plan, True, x, *params)
+        # Every BatchNorm block runs in its own module's mode (a trunk in eval() under model.train(), or the reverse): a
+        # forward that updates running statistics must not be run a second time by a recomputing backward
+        bn_training = any(cs.bn and cs.bnm.training for cs in plan.convs.values())
+        if need_grad and (self.training or bn_training):
+            return _DarknetFn.apply(plan, self.training, x, *params)
         if need_grad:
             # eval mode with autograd on (the reference's valid.py / test() never enter no_grad: their
             # `Variable(data, volatile=True)` is a no-op today): inference-speed forward, backward by recomputation
             return _DarknetEvalFn.apply(plan, x, *params)
-        if self.graph_inference and not self.training:
+        if self.graph_inference and not self.training and not bn_training:
             return plan.forward_graph(x)      # eval: the whole launch chain as one hipGraph replay
         return plan.forward(x, self.training)
 

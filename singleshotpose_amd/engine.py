@@ -15,7 +15,12 @@ map (M = B rows: the conv kernels, bias and activation path of a non-BN conv blo
 
 Backward mirrors it in reverse: ssp_bn_act_bwd (in place over the raw conv output) -> ssp_conv_wgrad ->
 ssp_unpack_grad, and ssp_conv_dgrad into the producer's gradient buffer (accumulating when a map has two consumers).
+
+Every BatchNorm block runs in its own module's mode (a trunk in eval() under model.train()), and a backward runs only what
+the parameters that want a gradient need: Plan.backward_schedule lists, per executed op, which launches that is; blocks
+no backward visits take the forward chain of a pass without gradient bookkeeping.
 """
+import collections
 import os
 import weakref
 
@@ -228,6 +233,12 @@ class _Act(object):
 
 INPUT = -1      # Plan.grads key (and _Act.producer) of the network input's gradient
 
+# One executed op of a backward pass (Plan.backward_schedule): `visited` = the op gets backward launches at all; `dgrad` =
+# per input map, whether a gradient is written into its producer; for conv blocks the filter gradient, the bias column sum,
+# which BatchNorm-parameter gradients are handed out, whether the BatchNorm-backward reductions run, and whether the
+# block's data gradient folds its producer's BatchNorm-backward sums (ssp_conv_dgrad_bnbwd).
+OpSchedule = collections.namedtuple('OpSchedule', 'ind kind visited dgrad wgrad bias dgamma dbeta bn_reduce fold_bn')
+
 
 class _Op(object):
     """One executed block other than a conv / connected block (those are _ConvSpec records): its kind ('maxpool',
@@ -264,6 +275,9 @@ class _ConvSpec(object):
     bnp = bn_fuse_src = None       # BatchNorm-backward sums folded into the consumer's dgrad (_plan_bn_fusion)
     v_live = False                 # the forward left the transformed input V in wino_ws for the filter gradient
     packed = False                 # the parameter is channels-last: used (and its gradient accumulated) in place
+    bn_train = False               # the last forward normalised this block with batch statistics (its BatchNorm's own mode)
+    has_raw = False                # ... and left the raw conv output behind (what a backward through the block needs)
+    fsched = None                  # the block's OpSchedule of the last forward that kept gradient bookkeeping
 
     @property
     def oind(self):
@@ -540,6 +554,7 @@ class Plan(object):
                                        # backward launch runs alone and its HIP-event duration is kernel-exclusive
         self.dgrad_ready = None
         self.grads = {}      # layer index -> _Act gradient buffers, allocated on first backward
+        self._schedules = {}     # backward schedules by what is trainable (_schedule)
         self.out_act = self.acts[self.last]
         self.out_flat = self.out_act.flat      # forward returns (B, C) instead of (B, C, h, w), as the reference
         self.consumed = False
@@ -626,7 +641,7 @@ class Plan(object):
                     cs.plan_fwd = assign[cs.ind]
                     self._size_layer(cs)
                 self._fit_workspace()
-                self._forward_body(True, False, False)
+                self._forward_body(True, False, False, bn_force=True)
                 return head()
             mom, self.bn_momentum = self.bn_momentum, 0.0
             try:
@@ -1306,7 +1321,11 @@ class Plan(object):
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, training, need_grad=False, inline_repack=False):
+    def forward(self, x, training, need_grad=False, inline_repack=False, trainable=None, want_input=True):
+        """training: the model's mode (the autograd node, the repack policy and the head budget follow it); every BatchNorm
+        block normalises by its OWN module's mode.  need_grad: a backward will follow - for the parameters whose ids are in
+        `trainable` (None = all of them) and, with want_input, the input: blocks that backward will not visit
+        (backward_schedule) run the chain of a forward without gradient bookkeeping."""
         B, H, W = self.B, self.H, self.W
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
@@ -1331,7 +1350,7 @@ class Plan(object):
         # (The whole training step as two captured hipGraphs was built and measured in round 4 - profiles/r04_step_graph.txt:
         # a replayed two-stream chain of ~300 nodes is SLOWER than launching it, 9.1 ms against 6.0 ms at batch 8 - and
         # removed in round 5: it mirrored this method's host-side state by hand.  Inference keeps its graph, forward_graph.)
-        self._forward_body(training, need_grad, inline_repack)
+        self._forward_body(training, need_grad, inline_repack, trainable=trainable, want_input=want_input)
         if training and getattr(self, '_hb_gains_after_forward', False):
             self._hb_gains_after_forward = False
             self._hb_gains = self._bn_gains()
@@ -1343,10 +1362,14 @@ class Plan(object):
         self.generation += 1
         return y
 
-    def _forward_body(self, training, need_grad, inline_repack):
+    def _forward_body(self, training, need_grad, inline_repack, bn_force=None, trainable=None, want_input=True):
+        """bn_force: None = every BatchNorm block in its module's own mode; True / False = all of them (the head budget
+        measures with batch statistics everywhere)."""
         B, H, W = self.B, self.H, self.W
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
+        for cs in self.convs.values():
+            cs.bn_train = bool(cs.bn and (cs.bnm.training if bn_force is None else bn_force))
         # Filter repacks depend only on the weights, not on the activations: they run on the side stream, ahead of the
         # convolutions that use them, instead of as one more dependent launch
         # in front of every conv on the main stream.  Forward operands first (two events: the first four layers, then
@@ -1370,7 +1393,14 @@ class Plan(object):
             elif training or self.wversion.get(cs.ind) != key:
                 stale.append((cs, key))
         if need_grad:
-            self._prepare_backward()
+            self._prepare_backward()        # (the schedule reads the BatchNorm fusion it plans)
+            sched = self._schedule(trainable, want_input, {cs.ind: cs.bn_train for cs in self.convs.values()})
+            for op, s_ in zip(self.ops, sched):
+                if op.kind == 'conv':
+                    op.fsched = s_
+        else:
+            for cs in self.convs.values():
+                cs.fsched = None
         # Winograd-plan layers read TRANSFORMED filters: re-derived when the weights may have changed (every training
         # step; in eval when a parameter version / the weights epoch moved), on the side stream like the repacks
         wino = []
@@ -1430,13 +1460,13 @@ class Plan(object):
             # and shares the chip badly - was measured: 26.17 / 25.93 ms against 25.85 / 25.97 ms as is, nothing)
             for ind in sorted(self.convs.keys(), reverse=True):
                 cs = self.convs[ind]
-                if not cs.first:
+                if not cs.first and cs.fsched.dgrad[0]:      # (a block whose producer gets no gradient needs no operand)
                     self._repack_dgrad(cs, side)
             self.dgrad_ready = side.record_event()
         else:
             self.dgrad_ready = None
         waited = set()
-        if training:
+        if any(cs.bn_train for cs in self.convs.values()):
             self.net._bn_epoch += 1       # running statistics change below: every plan's inference constants are stale
         for op in self.ops:
             kind = op.kind
@@ -1475,9 +1505,11 @@ class Plan(object):
             torch.cuda.current_stream().wait_event(ev)      # this layer's packed filters are ready
             waited.add(id(ev))
         bias = cs.conv.bias.data_ptr() if cs.conv.bias is not None else None
-        use_stats = cs.bn and training
+        bn_train = cs.bn_train                               # this block's own BatchNorm mode, not the model's
+        keep = cs.fsched is not None and cs.fsched.visited   # a backward will come through this block
+        use_stats = bn_train
         v = cs.vec
-        if cs.bn and not training:
+        if cs.bn and not bn_train:
             # inference-mode BatchNorm is a per-channel affine map of constants: recomputed only when one of
             # its four tensors changed (in-place updates bump _version; load_weights / fused SGD bump the epoch)
             bn = cs.bnm
@@ -1495,11 +1527,14 @@ class Plan(object):
         if wino_tile(cs.plan_fwd):
             wptr = self._wino_u(cs, wino_tile(cs.plan_fwd)).data_ptr()
         cs.first_live = False
-        if cs.first_fused and not cs.packed and (training or not need_grad):
+        cs.has_raw = False
+        if cs.first_fused and not cs.packed and (bn_train or not keep):
             # training: statistics pass + apply pass; inference: the apply pass alone with the running-statistics
             # affine (v[2], v[3] from ssp_bn_eval_prepare above) - conv + BN + leaky + pool in one launch, the
-            # full-resolution map is never written (672 x 672, batch 1: 12 us instead of 23 + 12)
-            if training:
+            # full-resolution map is never written (672 x 672, batch 1: 12 us instead of 23 + 12).  A BatchNorm in eval()
+            # under a training model takes the apply-only form when no backward comes through the block, else the generic
+            # kernels below (the fused backward passes are the batch-statistics ones).
+            if bn_train:
                 bn = cs.bnm
                 call('ssp_first_fwd_stats', cs.inp.ptr, wptr, cs.stats.data_ptr(), B, cs.H, cs.W, st)
                 call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.first_groups, cs.first_tile, cs.M, cs.cout,
@@ -1508,11 +1543,13 @@ class Plan(object):
                      v[2].data_ptr(), v[3].data_ptr(), st)
             call('ssp_first_fwd_apply', cs.inp.ptr, wptr, v[2].data_ptr(), v[3].data_ptr(), cs.slope,
                  cs.out.ptr, cs.out.ld, B, cs.H, cs.W, st)
-            cs.first_live = training        # only a training-mode forward can be followed by the fused backward
+            cs.first_live = bn_train        # only a batch-statistics forward can be followed by the fused backward
             return
-        if not training and not need_grad and cs.needs_act and not cs.pool and cs.coutp == cs.cout:
+        if (not bn_train and not keep and (cs.bn or not training) and cs.needs_act and not cs.pool and
+                cs.coutp == cs.cout):
             # inference, un-pooled block: BatchNorm affine + leaky folded into the conv epilogue - one launch,
-            # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps)
+            # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps).  Also
+            # a block with its BatchNorm in eval() that no backward will visit (a frozen trunk under model.train()).
             call('ssp_conv_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
                  v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld,
                  cs.out.ld, cs.k, cs.plan_fwd, self.ws.data_ptr(), self.ws_floats, st)
@@ -1520,11 +1557,13 @@ class Plan(object):
         ws_t = self.ws
         cs.v_live = False
         share_v = os.environ.get('SSP_WINO_SHARE_V', '1') != '0'
-        if (need_grad and wino_tile(cs.plan_fwd) and not wino_fused(cs.plan_fwd) and
+        cs.has_raw = True
+        want_v = keep and cs.fsched.wgrad      # the transformed input is kept for the filter gradient only
+        if (want_v and wino_tile(cs.plan_fwd) and not wino_fused(cs.plan_fwd) and
                 cs.wgrad_wino == wino_tile(cs.plan_fwd) and share_v):
             ws_t = self._wino_ws(cs)         # V stays at the head of this buffer for the layer's filter gradient
             cs.v_live = True
-        elif (need_grad and cs.wgrad_wino and share_v and self.side_stream is not None and
+        elif (want_v and cs.wgrad_wino and share_v and self.side_stream is not None and
                 os.environ.get('SSP_WINO_EARLY_V', '0') == '1'):
             # The filter gradient runs in the Winograd domain but this forward launch does not leave its V behind (the
             # error budget moved the layer to a direct code, or to the other tile size): the input transform the
@@ -1541,7 +1580,7 @@ class Plan(object):
         call('ssp_conv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias,
              cs.stats.data_ptr() if use_stats else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
              cs.k, 0, cs.plan_fwd, ws_t.data_ptr(), ws_t.numel(), st)
-        if cs.bn and training:
+        if bn_train:
             bn = cs.bnm
             call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.ntile, cs.tile_m, cs.M, cs.cout,
                  bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
@@ -1592,6 +1631,89 @@ class Plan(object):
         return self._y_static.clone()
 
     # ------------------------------------------------------------------ backward
+    def backward_schedule(self, trainable_ids=None, want_input=False, bn_training=None):
+        """What a backward pass runs, per executed op (one OpSchedule per entry of self.ops): pure bookkeeping, no launch.
+
+        trainable_ids: ids of the parameters that want a gradient (None = every parameter); want_input: the network input
+        wants one; bn_training: None = every BatchNorm module's own `training` flag, a bool = all of them, or
+        {conv layer index: bool}.
+
+        A block is upstream-relevant when it owns a trainable parameter or any map it reads derives from one that is (with
+        want_input the network input counts); it is visited iff it is upstream-relevant and reaches the output.  A data
+        gradient into a producer runs iff that producer is visited (or is the wanted input); filter gradient, bias column
+        sum, dgamma / dbeta follow their parameters; the BatchNorm-backward reductions of a visited block run when its
+        BatchNorm normalised with batch statistics (dx needs them) or gamma / beta is trainable - otherwise the block's
+        backward is the affine map's; a consumer's data gradient folds those sums only where they run."""
+        T = None if trainable_ids is None else frozenset(trainable_ids)
+
+        def has(p):
+            return p is not None and (T is None or id(p) in T)
+
+        def bn_mode(cs):
+            if not cs.bn:
+                return False
+            if bn_training is None:
+                return bool(cs.bnm.training)
+            if isinstance(bn_training, dict):
+                return bool(bn_training[cs.ind])
+            return bool(bn_training)
+
+        def srcs_of(op):
+            return [op.inp] if op.kind == 'conv' else op.srcs
+
+        rel = {INPUT: bool(want_input)}
+        own = {}
+        for op in self.ops:
+            mine = False
+            if op.kind == 'conv':
+                own[op.ind] = (has(op.conv.weight), has(op.conv.bias), bool(op.bn) and has(op.bnm.weight),
+                               bool(op.bn) and has(op.bnm.bias))
+                mine = any(own[op.ind])
+            rel[op.oind] = mine or any(rel[a.producer] for a in srcs_of(op))
+
+        def bn_reduce(cs):
+            return bool(cs.bn) and (bn_mode(cs) or own[cs.ind][2] or own[cs.ind][3])
+
+        reach = set([self.last])
+        out = [None] * len(self.ops)
+        for i in range(len(self.ops) - 1, -1, -1):
+            op = self.ops[i]
+            srcs = srcs_of(op)
+            if not (op.oind in reach and rel[op.oind]):
+                out[i] = OpSchedule(op.ind, op.kind, False, (False,) * len(srcs), False, False, False, False, False, False)
+                continue
+            dgrad = tuple(rel[a.producer] for a in srcs)
+            for a, d in zip(srcs, dgrad):
+                if d:
+                    reach.add(a.producer)
+            if op.kind != 'conv':
+                out[i] = OpSchedule(op.ind, op.kind, True, dgrad, False, False, False, False, False, False)
+                continue
+            w, b, dg, db = own[op.ind]
+            fold = bool(dgrad[0] and op.bn_fuse_src is not None and bn_reduce(op.bn_fuse_src))
+            out[i] = OpSchedule(op.ind, 'conv', True, dgrad, w, b, dg, db, bn_reduce(op), fold)
+        return out
+
+    def _schedule(self, trainable, want_input, modes=None):
+        """backward_schedule, remembered per (trainable set, want_input, BatchNorm modes): a training loop asks for the same
+        one every step."""
+        if modes is None:
+            modes = {cs.ind: bool(cs.bn and cs.bnm.training) for cs in self.convs.values()}
+        # (keyed by what the rules read - which parameters of which block are trainable - not by object ids, which a
+        # replaced parameter may reuse)
+        own = None if trainable is None else tuple(
+            tuple(p is not None and id(p) in trainable for p in (
+                cs.conv.weight, cs.conv.bias, cs.bnm.weight if cs.bn else None, cs.bnm.bias if cs.bn else None))
+            for cs in self.convs.values())
+        key = (own, bool(want_input), tuple(sorted(modes.items())), tuple(
+            None if cs.bn_fuse_src is None else cs.bn_fuse_src.ind for cs in self.convs.values()))
+        sched = self._schedules.get(key)
+        if sched is None:
+            if len(self._schedules) >= 32:
+                self._schedules.clear()
+            sched = self._schedules[key] = self.backward_schedule(trainable, want_input, modes)
+        return sched
+
     def _grad_buf(self, ind, like):
         g = self.grads.get(ind)
         if g is None:
@@ -1600,7 +1722,7 @@ class Plan(object):
             self.grads[ind] = g
         return g
 
-    def _dgrad(self, cs, src, dy_ptr, dy_ld, written, fused_stats, st):
+    def _dgrad(self, cs, src, dy_ptr, dy_ld, written, fused_stats, st, fold=True):
         """Data gradient of conv block `cs` into the gradient buffer of its input's producer `src` (with the producer's
         BatchNorm-backward sums folded in where _plan_bn_fusion arranged it)."""
         call = _lib.call
@@ -1609,7 +1731,7 @@ class Plan(object):
         scs = cs.bn_fuse_src
         dwt = (self._wino_ud(cs, wino_tile(cs.plan_dgrad)).data_ptr() if wino_tile(cs.plan_dgrad)
                else _ptr(self._dpack, cs.doff))
-        if scs is not None and src not in written:
+        if scs is not None and fold and src not in written:
             sv = scs.vec
             call('ssp_conv_dgrad_bnbwd', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W,
                  cs.coutp, cs.cin, dy_ld, gin.ld, cs.k, cs.plan_dgrad, self.ws.data_ptr(), self.ws_floats,
@@ -1626,9 +1748,21 @@ class Plan(object):
         """grad_out: (B, C, h, w) NCHW, or (B, C) when the network ends in avgpool / connected / softmax.  Returns
         ({param tensor id: grad tensor}, dL/dx as (B, in_c, H, W) fp32 or None).
 
-        want_input: also compute the gradient of the network input.  want_params=False (only with want_input): the
-        input-only backward - the data-gradient chain and the BatchNorm-backward reductions it needs, no filter / bias /
-        BatchNorm-parameter gradients, no flat gradient buffer, no reducer call; the dict is empty."""
+        want_input: also compute the gradient of the network input.  want_params: True = every parameter gets a gradient;
+        a collection of parameter ids = those parameters do, the others are frozen - the pass runs what
+        backward_schedule lists for them, the dict holds their gradients only and the frozen ranges of the flat
+        gradient buffer stay zero; False or empty (only with want_input): the input-only backward - the data-gradient
+        chain and the BatchNorm-backward reductions it needs, no filter / bias / BatchNorm-parameter gradients, no flat
+        gradient buffer, no reducer call; the dict is empty."""
+        if want_params is True:
+            trainable = None
+        elif want_params is False:
+            trainable = frozenset()
+        else:
+            trainable = frozenset(want_params) & frozenset(self.grad_layout)
+            if len(trainable) == len(self.grad_layout):
+                trainable = None
+        want_params = trainable is None or len(trainable) > 0
         if not (want_input or want_params):
             raise ValueError("Plan.backward: neither the input nor the parameter gradients are wanted")
         if self.consumed:
@@ -1646,8 +1780,15 @@ class Plan(object):
         call('ssp_nchw_to_nhwc', grad_out.data_ptr(), g_last.ptr, B, o.C, o.H, o.W, o.C, o.ld, st)
         if self.side_stream is None:
             self.side_stream = _side_stream(self.device)
+        # the BatchNorm modes are the ones the forward ran in, whatever the modules say by now
+        sched = self._schedule(trainable, want_input, {cs.ind: cs.bn_train for cs in self.convs.values()})
+        for op, s in zip(self.ops, sched):
+            if s.visited and op.kind == 'conv' and not (op.has_raw or op.first_live):
+                raise RuntimeError("Darknet backward: block %d was run without gradient bookkeeping by the last forward "
+                                   "(it was frozen then, or the forward ran in inference form) - its raw conv output "
+                                   "does not exist" % op.ind)
         if not want_params:
-            return self._backward_body(None, want_input)
+            return self._backward_body(None, want_input, sched)
         # ONE flat gradient buffer per model and device, reused by every backward of every plan (the layout depends on the
         # model only): the returned gradients are views of it.  Reuse is safe only while nothing else still views the
         # buffer (optimizer.zero_grad(set_to_none=True) - torch's default - drops the .grad views; a caller that keeps or
@@ -1662,10 +1803,10 @@ class Plan(object):
             self.net._flat_grads[self.device] = (flat, _storage_refs(flat))
         flat.record_stream(self.side_stream)
         self.last_flat_grad = flat
-        return self._backward_body(flat, want_input)
+        return self._backward_body(flat, want_input, sched)
 
-    def _backward_body(self, flat, want_input):
-        """flat None: input-only backward (see backward)."""
+    def _backward_body(self, flat, want_input, sched):
+        """flat None: input-only backward (see backward).  sched: the pass's backward_schedule."""
         B = self.B
         st = torch.cuda.current_stream().cuda_stream
         call = _lib.call
@@ -1674,9 +1815,10 @@ class Plan(object):
         written.add(self.last)
         if flat is not None:
             flat.zero_()
-            for cs in self.convs.values():          # gradient staging of the parameters that are not channels-last
-                if not cs.packed and not cs.first_live:      # (the fused first block's filter gradient is WRITTEN, not accumulated)
-                    self._gbuf(cs).zero_()
+            for op, s in zip(self.ops, sched):      # gradient staging of the parameters that are not channels-last
+                # (the fused first block's filter gradient is WRITTEN, not accumulated)
+                if s.wgrad and not op.packed and not op.first_live:
+                    self._gbuf(op).zero_()
         # Filter gradients run on a second stream: wgrad(l) only needs dY(l) and the saved input activation, so it
         # overlaps the dgrad(l) -> BN-backward(l-1) chain of the main stream and fills the idle CUs of its last wave.
         main = torch.cuda.current_stream()
@@ -1685,9 +1827,10 @@ class Plan(object):
             main.wait_event(self.dgrad_ready)       # dgrad filter repacks were queued during forward
         else:
             self._prepare_backward(tune=False)      # the saved conv outputs are live: no timing / verify launches now
+            by_ind = {s.ind: s for s in sched if s.kind == 'conv'}
             for ind in sorted(self.convs.keys(), reverse=True):   # forward ran without grad bookkeeping: repack now
                 cs = self.convs[ind]
-                if not cs.first:
+                if not cs.first and by_ind[ind].dgrad[0]:
                     self._repack_dgrad(cs, main)
         out_grads = {}
         tail_sched = side is not main and os.environ.get('SSP_TAIL_SCHED', '1') != '0'
@@ -1707,27 +1850,38 @@ class Plan(object):
             written.add(a.producer)
             return gin, acc
 
-        for op in reversed(self.ops):
-            if op.oind not in written:
-                continue          # nothing downstream of this block reaches the output
+        def grad_scratch(a):
+            """... of a producer that gets no gradient (a frozen branch): its buffer is written and never read."""
+            return self._grad_buf(a.producer, a), 0
+
+        for op, s in zip(reversed(self.ops), reversed(sched)):
+            if not s.visited or op.oind not in written:
+                # nothing downstream of this block reaches the output, or nothing upstream of it wants a gradient: no
+                # launch - its (zero) range of the flat buffer is complete, and the reducer's buckets close in order
+                if op.kind == 'conv' and flat is not None and self.reducer is not None:
+                    with torch.cuda.stream(side):
+                        self.reducer.layer_done(flat, op.grad_lo, op.grad_hi)
+                continue
             g = self.grads[op.oind]
             kind = op.kind
             if kind == 'conv':
-                self._conv_bwd(op, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched, want_input)
+                self._conv_bwd(op, s, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched)
             elif kind == 'shortcut':
                 a, b = op.srcs
-                ga, acc_a = grad_in(a)
-                gb, acc_b = (ga, acc_a) if b is a else grad_in(b)     # (from = -1: one buffer - the kernel adds 2 g')
+                ga, acc_a = grad_in(a) if s.dgrad[0] else grad_scratch(a)
+                # (from = -1: one buffer - the kernel adds 2 g')
+                gb, acc_b = (ga, acc_a) if b is a else (grad_in(b) if s.dgrad[1] else grad_scratch(b))
                 out = op.out
                 call('ssp_shortcut_bwd', g.ptr, g.ld, out.ptr, out.ld, ga.ptr, ga.ld, acc_a, gb.ptr, gb.ld, acc_b,
                      _pad4(out.C), B * out.H * out.W, op.slope, st)
             elif kind in ('alias', 'concat'):
                 off = 0
-                for a in op.srcs:
-                    gin, acc = grad_in(a)
-                    call('ssp_copy_channels', _ptr(g.t, g.off + off), g.ld, gin.ptr, gin.ld, a.C, B * a.H * a.W, acc, st)
+                for a, d in zip(op.srcs, s.dgrad):
+                    if d:
+                        gin, acc = grad_in(a)
+                        call('ssp_copy_channels', _ptr(g.t, g.off + off), g.ld, gin.ptr, gin.ld, a.C, B * a.H * a.W, acc, st)
                     off += a.C
-            else:
+            elif s.dgrad[0]:
                 src = op.srcs[0]
                 gin, acc = grad_in(src)
                 if kind in ('maxpool', 'maxpool_s1'):
@@ -1753,130 +1907,130 @@ class Plan(object):
             main.wait_stream(side)              # every filter gradient is complete before autograd hands them out
         return out_grads, dx
 
-    def _conv_bwd(self, cs, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched, want_input):
-        """Backward launches of conv block `cs` from the gradient g of its (pooled) output: BatchNorm / activation backward,
-        bias gradient, filter gradient on the side stream, data gradient into the producer of its input (for the first
-        block: into the input's gradient buffer, when want_input).  flat None: input-only backward, no parameter
-        gradient work."""
+    def _conv_bwd(self, cs, s, g, flat, gview, out_grads, written, fused_stats, main, side, tail_sched):
+        """Backward launches of conv block `cs` from the gradient g of its (pooled) output, as its schedule entry `s` lists
+        them: BatchNorm / activation backward, bias gradient, filter gradient on the side stream, data gradient into the
+        producer of its input (for the first block: into the input's gradient buffer).  flat None: input-only backward,
+        no parameter gradient work."""
         B = self.B
         call = _lib.call
         st, st2 = main.cuda_stream, side.cuda_stream
-        training = self.was_training
+        training = cs.bn_train          # the mode this block's forward ran in
         v = cs.vec
         params = flat is not None
-        if cs.first_live and not params:
-            # input-only, fused first block: the reductions dy_raw needs (dgamma / dbeta land in scratch), then dL/dx
-            wptr = self._wbuf(cs).data_ptr()
-            call('ssp_first_bwd_reduce', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
-                 v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
-            call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
-                 1 if training else 0, 0, v[6].data_ptr(), v[7].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
-            self._first_input_dgrad(cs, g, written, st)
-            return
+
+        def hand_out(prm):
+            gv = gview(prm)
+            out_grads[id(prm)] = gv
+            return gv
+
         if cs.first_live:
-            # first block, fused form: both backward passes recompute the convolution from the input
-            dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
-            out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
+            # first block, fused form: every backward pass recomputes the convolution from the input.  The reductions
+            # feed dy_raw, which each of the passes below needs (a frozen gamma / beta lands in scratch).
+            dg_ptr = hand_out(cs.bnm.weight).data_ptr() if s.dgamma else v[6].data_ptr()
+            db_ptr = hand_out(cs.bnm.bias).data_ptr() if s.dbeta else v[7].data_ptr()
             wptr = self._wbuf(cs).data_ptr()
             call('ssp_first_bwd_reduce', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
                  v[0].data_ptr(), v[1].data_ptr(), cs.slope, cs.first_partial.data_ptr(), B, cs.H, cs.W, st)
             call('ssp_bn_bwd_finalize', cs.first_partial.data_ptr(), cs.first_groups, cs.cout, cs.M,
-                 1 if training else 0, 0, dgam.data_ptr(), dbet.data_ptr(), v[4].data_ptr(), v[5].data_ptr(), st)
-            if want_input:          # main stream, after the finalize: it reads what the filter gradient below reads
+                 1 if training else 0, 0, dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+            if s.dgrad[0]:          # main stream, after the finalize: it reads what the filter gradient below reads
                 self._first_input_dgrad(cs, g, written, st)
+            if not params:
+                return
             # The step's tail is a dependency chain: dgrad of the block's consumer -> this reduce -> this filter
             # gradient (HBM-bound: it re-reads the 1.4 GB output gradient).  With the tail schedule the consumer's
             # filter gradient (MFMA-bound) was held back behind its data gradient and is running on the side
             # stream NOW: this pass stays on the main stream and overlaps it, instead of queueing behind it.
             fst = st if tail_sched else st2
-            if not tail_sched:
-                side.wait_stream(main)
-            gw = gview(cs.conv.weight, False)
-            if cs.first_wpart is None:      # per-workgroup partial gradients, summed in float64
-                cs.first_wpart = torch.empty(_lib.query('ssp_first_wgrad_workspace_floats', B, cs.H, cs.W),
-                                             dtype=torch.float32, device=self.device)
-            call('ssp_first_bwd_wgrad', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
-                 v[0].data_ptr(), v[1].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), cs.slope,
-                 self._gbuf(cs).data_ptr(), cs.first_wpart.data_ptr(), cs.first_wpart.numel(), B, cs.H, cs.W, fst)
-            call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, fst)
-            out_grads[id(cs.conv.weight)] = gw
+            if s.wgrad:
+                if not tail_sched:
+                    side.wait_stream(main)
+                gw = gview(cs.conv.weight, False)
+                if cs.first_wpart is None:      # per-workgroup partial gradients, summed in float64
+                    cs.first_wpart = torch.empty(_lib.query('ssp_first_wgrad_workspace_floats', B, cs.H, cs.W),
+                                                 dtype=torch.float32, device=self.device)
+                call('ssp_first_bwd_wgrad', cs.inp.ptr, wptr, g.ptr, g.ld, v[2].data_ptr(), v[3].data_ptr(),
+                     v[0].data_ptr(), v[1].data_ptr(), v[4].data_ptr(), v[5].data_ptr(), cs.slope,
+                     self._gbuf(cs).data_ptr(), cs.first_wpart.data_ptr(), cs.first_wpart.numel(), B, cs.H, cs.W, fst)
+                call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, fst)
+                out_grads[id(cs.conv.weight)] = gw
             if self.reducer is not None:
-                if tail_sched:
+                if tail_sched or not s.wgrad:
                     side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
             return
         if cs.needs_act:
-            if cs.bn and cs.coutp == cs.cout and params:
-                dgam, dbet = gview(cs.bnm.weight), gview(cs.bnm.bias)
-                out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = dgam, dbet
-                dg_ptr, db_ptr = dgam.data_ptr(), dbet.data_ptr()
+            if cs.bn and not s.bn_reduce:
+                # BatchNorm in eval() with gamma and beta frozen: the block is an affine map + activation, its backward
+                # one apply pass - no reduction, no finalize
+                call('ssp_bn_act_bwd_affine', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(), cs.ldraw,
+                     v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B, cs.H, cs.W,
+                     1 if cs.pool else 0, cs.slope, st)
+            else:
                 # two-level reduction (per-workgroup partials -> fp64 finalize).  The single-pass form of
                 # ssp_bn_act_bwd (atomics into the zeroed gradient, no finalize launch) measured 1.1 ms SLOWER
                 # per step: 1024 workgroups hammering the same 2*C addresses serialise in the L2.
+                direct = cs.bn and cs.coutp == cs.cout      # the reductions land in the gradients themselves
+                dg_ptr = hand_out(cs.bnm.weight).data_ptr() if (direct and s.dgamma) else v[6].data_ptr()
+                db_ptr = hand_out(cs.bnm.bias).data_ptr() if (direct and s.dbeta) else v[7].data_ptr()
                 partial = self.bn_partial.data_ptr()
-            else:
-                dg_ptr, db_ptr = v[6].data_ptr(), v[7].data_ptr()
-                partial = self.bn_partial.data_ptr()
-            if cs.ind in fused_stats:
-                # the two reductions came out of the consumer's data-gradient launch: finalize + apply only
-                ptile, rows, folded = cs.bnp
-                call('ssp_bn_act_bwd_partials', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(),
-                     cs.ldraw, v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B,
-                     cs.H, cs.W, cs.slope, 1 if training else 0, ptile.data_ptr(), rows, 1 if folded else 0,
-                     dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
-            else:
-                call('ssp_bn_act_bwd', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(), cs.ldraw,
-                     v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B, cs.H, cs.W,
-                     1 if cs.pool else 0, cs.slope, 1 if (training and cs.bn) else 0, partial,
-                     dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+                if cs.ind in fused_stats:
+                    # the two reductions came out of the consumer's data-gradient launch: finalize + apply only
+                    ptile, rows, folded = cs.bnp
+                    call('ssp_bn_act_bwd_partials', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(),
+                         cs.ldraw, v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B,
+                         cs.H, cs.W, cs.slope, 1 if training else 0, ptile.data_ptr(), rows, 1 if folded else 0,
+                         dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+                else:
+                    call('ssp_bn_act_bwd', cs.raw.data_ptr(), cs.ldraw, g.ptr, g.ld, cs.raw.data_ptr(), cs.ldraw,
+                         v[2].data_ptr(), v[3].data_ptr(), v[0].data_ptr(), v[1].data_ptr(), cs.coutp, B, cs.H, cs.W,
+                         1 if cs.pool else 0, cs.slope, 1 if training else 0, partial,
+                         dg_ptr, db_ptr, v[4].data_ptr(), v[5].data_ptr(), st)
+                if cs.bn and not direct:
+                    if s.dgamma:
+                        hand_out(cs.bnm.weight).copy_(v[6][:cs.cout])
+                    if s.dbeta:
+                        hand_out(cs.bnm.bias).copy_(v[7][:cs.cout])
             dy_ptr, dy_ld = cs.raw.data_ptr(), cs.ldraw
-            if cs.bn and cs.coutp != cs.cout and params:
-                gview(cs.bnm.weight).copy_(v[6][:cs.cout])
-                gview(cs.bnm.bias).copy_(v[7][:cs.cout])
-                out_grads[id(cs.bnm.weight)], out_grads[id(cs.bnm.bias)] = gview(cs.bnm.weight), gview(cs.bnm.bias)
         else:
             dy_ptr, dy_ld = g.ptr, g.ld
-        if not params:
-            # input-only: the data-gradient chain alone
-            if cs.first:
-                self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
-            else:
-                self._dgrad(cs, cs.inp.producer, dy_ptr, dy_ld, written, fused_stats, st)
-            return
-        if cs.conv.bias is not None:
-            db = gview(cs.conv.bias)
+        if s.bias:
+            db = hand_out(cs.conv.bias)
             call('ssp_colsum', dy_ptr, dy_ld, cs.M, cs.cout, db.data_ptr(), st)
-            out_grads[id(cs.conv.bias)] = db
         src = None if cs.first else cs.inp.producer
         # tail schedule: the consumer of the fused first block (layer 2) runs its data gradient - the head of the
         # chain that ends the step - BEFORE its filter gradient is released on the side stream
         owner = None if src is None else (self.convs.get(src - 1) if src in self.fused_pool else self.convs.get(src))
-        defer = tail_sched and owner is not None and owner.first_live
+        defer = params and tail_sched and owner is not None and owner.first_live and s.dgrad[0]
         if defer:
-            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
-        side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
-        gw = gview(cs.conv.weight, cs.packed)
-        if cs.packed and cs.wgrad_wino:
-            wws = self._wino_ws(cs)
-            call('ssp_conv_wgrad_wino_t', dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(),
-                 B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(), wws.numel(), st2)
-            cs.v_live = False
-        elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
-            call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
-                 cs.inp.ld, cs.k, st2)
-        else:
-            call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.H, cs.W, cs.cinp,
-                 cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
-            call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
-        out_grads[id(cs.conv.weight)] = gw
-        if self.reducer is not None:
+            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn)
+        if params:
+            side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
+        if s.wgrad:
+            gw = gview(cs.conv.weight, cs.packed)
+            if cs.packed and cs.wgrad_wino:
+                wws = self._wino_ws(cs)
+                call('ssp_conv_wgrad_wino_t', dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(),
+                     B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(), wws.numel(), st2)
+                cs.v_live = False
+            elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
+                call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
+                     cs.inp.ld, cs.k, st2)
+            else:
+                call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.H, cs.W, cs.cinp,
+                     cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
+                call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
+            out_grads[id(cs.conv.weight)] = gw
+        if params and self.reducer is not None:
             with torch.cuda.stream(side):   # the all-reduce of a finished bucket is ordered after its wgrads
                 self.reducer.layer_done(flat, cs.grad_lo, cs.grad_hi)
-        if not cs.first and not defer:
-            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st)
-        elif cs.first and want_input:
-            self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
+        if s.dgrad[0] and not defer:
+            if cs.first:
+                self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
+            else:
+                self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn)
 
     def _input_gbuf(self, written):
         """The input's gradient buffer, NHWC [B*H*W][in_cp], and whether a launch accumulates into it (marks it written)."""
@@ -1914,6 +2068,11 @@ class Plan(object):
                   self.B, cs.H, cs.W, st)
 
 
+def _trainable(params, needs):
+    """ids of the parameters autograd wants a gradient for."""
+    return frozenset(id(p) for p, n in zip(params, needs) if n)
+
+
 class _DarknetFn(torch.autograd.Function):
     """One autograd node for the whole network: forward/backward are sequences of HIP launches."""
 
@@ -1921,7 +2080,8 @@ class _DarknetFn(torch.autograd.Function):
     def forward(ctx, plan, training, x, *params):
         ctx.plan = plan
         ctx.params = params
-        y = plan.forward(x, training, need_grad=True)
+        need = ctx.needs_input_grad
+        y = plan.forward(x, training, need_grad=True, trainable=_trainable(params, need[3:]), want_input=need[2])
         ctx.generation = plan.generation
         return y
 
@@ -1935,8 +2095,8 @@ class _DarknetFn(torch.autograd.Function):
             raise RuntimeError("Darknet backward after a newer forward on the same input shape: the plan's saved "
                                "activations were overwritten")
         want_x = ctx.needs_input_grad[2]
-        want_p = any(ctx.needs_input_grad[3:])
-        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p or not want_x)
+        want_p = _trainable(ctx.params, ctx.needs_input_grad[3:])
+        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p if (want_p or want_x) else True)
         # Until its backward has run the node keeps its plan alive (forward at shape A, forward at shape B, backward of A
         # works whatever the cache evicted).  Afterwards only the cache does: a caller that still holds the loss tensor of the
         # previous resolution (every training loop does, until it assigns the next one) must not keep that resolution's
@@ -1969,10 +2129,13 @@ class _DarknetEvalFn(torch.autograd.Function):
         plan = ctx.plan
         if ctx.x._version != ctx.xver:
             raise RuntimeError("Darknet (eval mode) backward: the input tensor was modified in place after the forward")
-        plan.forward(ctx.x, False, need_grad=True)      # recompute, keeping the raw conv outputs
         want_x = ctx.needs_input_grad[1]
-        want_p = any(ctx.needs_input_grad[2:])
-        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p or not want_x)
+        want_p = _trainable(ctx.params, ctx.needs_input_grad[2:])
+        if not (want_p or want_x):
+            want_p = _trainable(ctx.params, [True] * len(ctx.params))
+        # recompute, keeping the raw conv outputs of the blocks the backward visits
+        plan.forward(ctx.x, False, need_grad=True, trainable=want_p, want_input=want_x)
+        grads, dx = plan.backward(grad_out.contiguous(), want_input=want_x, want_params=want_p)
         res = [None, dx]
         for p in ctx.params:
             res.append(grads.get(id(p)))
