@@ -20,10 +20,10 @@ import socket
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import topology_cases as T
 from helpers import GOLD, ROOT, load_state_into, rel_err
+from sequence_cases import _ref_forward
 from test_finetune_cpu import _expected, _own
 
 pytestmark = pytest.mark.gpu
@@ -69,42 +69,6 @@ def _input(cfg, seed=1):
 
 def _probe(y, seed=5):
     return torch.from_numpy(np.random.RandomState(seed).standard_normal(tuple(y.shape)).astype(np.float32))
-
-
-def _ref_forward(blocks, mods, x, frozen=None):
-    """The reference's block semantics (darknet.py:82-130) on `mods` as they are - no .train() / .eval() call.  frozen: the
-    product's decisions (_decisions), applied as oracle.darknet_ref.forward_ref applies them."""
-    raw, act, pool = ((frozen or {}).get(k) or {} for k in ('raw_override', 'act_override', 'pool_override'))
-    outputs = {}
-    for ind, b in enumerate(blocks[1:]):
-        t = b['type']
-        if t == 'convolutional':
-            for m in mods[ind]:
-                if isinstance(m, torch.nn.LeakyReLU) and ind in act:
-                    x = torch.where(act[ind] > 0, x, x * 0.1)
-                    continue
-                x = m(x)
-                if isinstance(m, torch.nn.Conv2d) and ind in raw:
-                    x = raw[ind].to(x.dtype) + (x - x.detach())
-        elif t == 'maxpool' and ind in pool:
-            x = x.flatten(2).gather(2, pool[ind].flatten(2)).view(pool[ind].shape)
-        elif t == 'maxpool':
-            x = F.max_pool2d(x, int(b['size']), int(b['stride']))
-        elif t == 'reorg':
-            x = T.reorg2(x)
-        elif t == 'route':
-            ls = T._resolve(b['layers'], ind)
-            x = outputs[ls[0]] if len(ls) == 1 else torch.cat([outputs[l] for l in ls], 1)
-        elif t == 'shortcut':
-            x = outputs[T._resolve(b['from'], ind)[0]] + outputs[ind - 1]
-            if b['activation'] in ('leaky', 'relu'):
-                x = F.leaky_relu(x, 0.1) if b['activation'] == 'leaky' else F.relu(x)
-        elif t in ('region', 'cost'):
-            continue
-        else:
-            raise NotImplementedError(t)
-        outputs[ind] = x
-    return x
 
 
 def _reference(model, x, probe=None, frozen=None):
