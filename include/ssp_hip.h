@@ -110,6 +110,37 @@ int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int
                          const float* raw, int ldraw, const float* scale, const float* shift, const float* mean,
                          const float* invstd, float slope, float* partial, int partial_rows, void* stream);
 
+/* The data gradient of a 3x3 layer as the ADJOINT of the Winograd forward map (appended to ABI 5; csrc/conv_wino.hip
+ * wino_dgrad_finish_kernel).  The adjoint of Y = A^T [U (.) (B^T d B)] A is, per tile,
+ *   dd = B [ sum_co U_xi[co][ci] * (A dY A^T)_xi[co] ] B^T,     dX = overlap-add of the (tile+2) x (tile+2) windows dd,
+ * so it contracts dM = A dY A^T - the planes the Winograd filter gradient of the same layer and tile size transforms dY
+ * into anyway - with the FORWARD filter transform, channels transposed; no B^T dY B planes and no second transform of dY.
+ * Same result as the data gradient entry points above with the same plan, to fp32 rounding (~5e-6 of the range at tile 4).
+ *   ssp_wino_outgrad_transform_t: dM [(tile+2)^2][tiles][C] = A dY A^T of dy [B*H*W][lddy], tile 2 or 4, C % 4 == 0; timed
+ *     with the Winograd data-gradient family.  Into the dM slot of a filter-gradient workspace (V | dM | dU: offset
+ *     (tile+2)^2 * tiles * Cin floats) it feeds BOTH gradients: ssp_conv_wgrad_wino_t then takes dy == NULL (tiles 2 and 4
+ *     only; tile 12 keeps dM on the chip and refuses it).
+ *   ssp_wino_filter_transform_adj_t: Ut[xi][row][k] = (G g G^T)[xi] of the UN-flipped filters out of the data-gradient
+ *     layout w9d [rows = Cin_dx][tap][K = Cout_dy] (ssp_repack_dgrad, whose taps are rotated by 180 degrees): bit for bit
+ *     the forward transform of the same filters packed [Cin_dx][tap][Cout_dy] without the rotation.
+ *   ssp_conv_dgrad_adj / ssp_conv_dgrad_adj_bnbwd: the arguments, epilogues and limits of the two data gradient entry points
+ *     above, with wt = Ut, plan = a through-memory Winograd code (8xxxxxx / 9xxxxxx: tile rows, ring slots; any other code
+ *     is an error) and dM: the transformed output gradient [(tile+2)^2][tiles][Cout_dy] (dy is then not read), or NULL =
+ *     transform dy here.  One batched GEMM launch dV_xi[tiles][Cin_dx] = dM_xi * Ut_xi^T and the finishing pass.
+ *     workspace: ssp_conv_dgrad_adj_workspace_floats(..., own_dm = (dM == NULL)) floats, dV | (own dM); never more than
+ *     ssp_conv_workspace_floats of the same plan. */
+int ssp_wino_outgrad_transform_t(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, void* stream);
+int ssp_wino_filter_transform_adj_t(const float* w9d, float* Ut, int rows, int K, int tile, void* stream);
+int64_t ssp_conv_dgrad_adj_workspace_floats(int B, int H, int W, int Cout_dy, int Cin_dx, int plan, int own_dm);
+int ssp_conv_dgrad_adj(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                       int lddx, int R, int accumulate, int plan, float* workspace, int64_t workspace_floats,
+                       const float* dM, void* stream);
+int ssp_conv_dgrad_adj_bnbwd(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
+                             int lddy, int lddx, int R, int plan, float* workspace, int64_t workspace_floats,
+                             const float* raw, int ldraw, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, float slope, float* partial, int partial_rows, const float* dM,
+                             void* stream);
+
 /* filter gradient: dw[co][tap][ci] += sum_p dy[p][co] * x[p + tap][ci]; dw is [Cout][R*R][Cin] packed and must be
  * zeroed by the caller (split reduction uses fp32 atomics). */
 int ssp_conv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,

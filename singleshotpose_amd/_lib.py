@@ -39,6 +39,11 @@ _SIGS = {
     "ssp_wino_filter_transform_t": [P, P, I, I, I, P],
     "ssp_conv_dgrad": [P, P, P, I, I, I, I, I, I, I, I, I, I, P, L, P],
     "ssp_conv_dgrad_bnbwd": [P, P, P, I, I, I, I, I, I, I, I, I, P, L, P, I, P, P, P, P, F, P, I, P],
+    "ssp_wino_outgrad_transform_t": [P, I, P, I, I, I, I, I, P],
+    "ssp_wino_filter_transform_adj_t": [P, P, I, I, I, P],
+    "ssp_conv_dgrad_adj_workspace_floats": [I, I, I, I, I, I, I],
+    "ssp_conv_dgrad_adj": [P, P, P, I, I, I, I, I, I, I, I, I, I, P, L, P, P],
+    "ssp_conv_dgrad_adj_bnbwd": [P, P, P, I, I, I, I, I, I, I, I, I, P, L, P, I, P, P, P, P, F, P, I, P, P],
     "ssp_bn_act_bwd_partials": [P, I, P, I, P, I, P, P, P, P, I, I, I, I, F, I, P, I, I, P, P, P, P, P],
     "ssp_conv_wgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
     "ssp_conv_wgrad_route": [I, I, I, I, I, I, I, I],
@@ -103,7 +108,7 @@ _SIGS = {
     "ssp_prof_collect": [P, P, P],
 }
 
-_RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',
+_RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_dgrad_adj_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',
           'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles')
 
 PROF_KINDS = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_act", "layout", "region", "optim", "first_block_fwd",

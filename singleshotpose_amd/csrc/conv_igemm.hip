@@ -510,9 +510,17 @@ int64_t ssp_conv_ws_floats(int M, int Cin, int Cout, int R, int plan) {
 int64_t ssp_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile) {
   return ssp_wino_planes(tile) * ssp_wino_tiles(B, H, W, tile) * ((int64_t)Cin + Cout);
 }
+// The ADJOINT form of the data gradient (ssp_conv_dgrad_adj; a.Cin = channels of dy, a.Cout = channels of dx): `wt` is the
+// forward filter transform with the channels transposed, Ut [P][Cin_dx][Cout_dy] (ssp_wino_filter_transform_adj_t), the
+// GEMM operand is dM = A dY A^T [P][T][Cout_dy] - the caller's (the filter gradient's own copy, `dM`) or, dM == nullptr,
+// transformed here into the workspace - and the finishing pass gathers B dV B^T over the neighbouring tiles
+// (wino_dgrad_finish_kernel).  Workspace: dV [P][T][Cin_dx] | (dM == nullptr only) dM [P][T][Cout_dy].
+int64_t ssp_wino_adj_ws_floats(int B, int H, int W, int Cout_dy, int Cin_dx, int tile, bool own_dm) {
+  return ssp_wino_planes(tile) * ssp_wino_tiles(B, H, W, tile) * ((int64_t)Cin_dx + (own_dm ? Cout_dy : 0));
+}
 
 static int wino_launch(ConvArgs& a, int B, int H, int W, float* ws, int64_t ws_floats, int plan, int prof_kind,
-                       hipStream_t stream) {
+                       hipStream_t stream, bool adj = false, const float* dM = nullptr) {
   const int bm = (plan / 100) % 1000, slots = plan % 10, tile = ssp_wino_plan_tile(plan), P = ssp_wino_planes(tile);
   SSP_CHECK_ARG(a.R == 3 && a.Cin % 16 == 0 && a.Cout >= 64 && a.Cout % 4 == 0 && a.ldout % 4 == 0 && (((uintptr_t)a.out) & 15) == 0,
                 "conv (Winograd plan): needs a 3x3 filter, Cin %% 16 == 0, Cout >= 64 and %% 4 == 0, an aligned output");
@@ -520,16 +528,27 @@ static int wino_launch(ConvArgs& a, int B, int H, int W, float* ws, int64_t ws_f
                     (plan / 100000) % 10 == 0, "conv: bad Winograd plan code %d", plan);
   const int64_t T = ssp_wino_tiles(B, H, W, tile);
   SSP_CHECK_ARG(T < (1ll << 31) && P * T * (int64_t)a.Cin < (1ll << 40), "conv (Winograd plan): too many tiles");
-  SSP_CHECK_ARG(ws != nullptr && ws_floats >= ssp_wino_ws_floats(B, H, W, a.Cin, a.Cout, tile) && (((uintptr_t)ws) & 15) == 0,
-                "conv (Winograd plan): needs a workspace of %lld floats (ssp_conv_workspace_floats)",
-                (long long)ssp_wino_ws_floats(B, H, W, a.Cin, a.Cout, tile));
+  const int64_t need = adj ? ssp_wino_adj_ws_floats(B, H, W, a.Cin, a.Cout, tile, dM == nullptr)
+                           : ssp_wino_ws_floats(B, H, W, a.Cin, a.Cout, tile);
+  SSP_CHECK_ARG(ws != nullptr && ws_floats >= need && (((uintptr_t)ws) & 15) == 0,
+                "conv (Winograd plan): needs a workspace of %lld floats (ssp_conv_workspace_floats)", (long long)need);
+  SSP_CHECK_ARG((((uintptr_t)dM) & 15) == 0, "conv (Winograd plan): dM must be 16-byte aligned");
   SSP_CHECK_ARG((int64_t)(128 + 2) * a.Cin * 4 + (int64_t)a.Cin * 4 < (1ll << 31), "conv (Winograd plan): Cin too large");
   if (a.bn_partial != nullptr) SSP_CHECK_ARG(a.bn_ld % 4 == 0, "conv (Winograd plan): bn_ld must be a multiple of 4");
   SspProfScope prof(prof_kind, stream, 2.0 * (double)a.M * a.Cout * 9.0 * a.Cin);      // algorithmic (direct) FLOPs
-  float* V = ws;
+  const float* V = ws;
   float* Mw = ws + P * T * a.Cin;
   const int wkind = prof_kind == SSP_PROF_CONV_DGRAD ? SSP_PROF_WINO_DGRAD : SSP_PROF_WINO_FWD;
-  if (int rc = ssp_wino_input_launch(a.in, a.ldin, V, B, H, W, a.Cin, tile, wkind, stream)) return rc;
+  if (adj) {
+    Mw = ws;                  // dV
+    V = dM;
+    if (dM == nullptr) {
+      SSP_CHECK_ARG(a.in != nullptr, "conv (adjoint data gradient): dy must be given when dM is NULL");
+      float* own = ws + P * T * a.Cout;
+      if (int rc = ssp_wino_outgrad_launch(a.in, a.ldin, own, B, H, W, a.Cin, tile, stream, wkind)) return rc;
+      V = own;
+    }
+  } else if (int rc = ssp_wino_input_launch(a.in, a.ldin, ws, B, H, W, a.Cin, tile, wkind, stream)) return rc;
   ConvArgs g = a;
   g.in = V; g.wt = a.wt; g.out = Mw; g.bias = nullptr; g.escale = nullptr; g.act_slope = 1.f; g.stats = nullptr;
   g.H = 1; g.W = (int)T; g.ldin = a.Cin; g.ldout = a.Cout; g.R = 1; g.M = (int)T; g.accumulate = 0;
@@ -543,13 +562,13 @@ static int wino_launch(ConvArgs& a, int B, int H, int W, float* ws, int64_t ws_f
   o.Cout = a.Cout; o.ldout = a.ldout; o.accumulate = a.accumulate;
   o.bn_raw = a.bn_raw; o.bn_scale = a.bn_scale; o.bn_shift = a.bn_shift; o.bn_mean = a.bn_mean; o.bn_invstd = a.bn_invstd;
   o.bn_partial = a.bn_partial; o.bn_nslot = a.bn_nslot; o.bn_ld = a.bn_ld; o.bn_slope = a.bn_slope;
-  return ssp_wino_output_launch(o, B, H, W, tile, wkind, stream);
+  return ssp_wino_output_launch(o, B, H, W, tile, wkind, stream, adj);
 }
 
 int ssp_conv_igemm_launch(const float* in, const float* wt, float* out, const float* bias, float* stats, int B, int H,
                           int W, int Cin, int Cout, int ldin, int ldout, int R, int accumulate, float* ws,
                           int64_t ws_floats, int plan, int prof_kind, hipStream_t stream, const float* escale,
-                          float act_slope, const SspBnBwdFuse* bnb) {
+                          float act_slope, const SspBnBwdFuse* bnb, bool adj, const float* dM) {
   SSP_CHECK_ARG(R == 1 || R == 3, "conv: only 1x1 and 3x3 filters are supported (got %d)", R);
   SSP_CHECK_ARG(Cin % 4 == 0 && Cin > 0, "conv: Cin must be a positive multiple of 4 (got %d)", Cin);
   SSP_CHECK_ARG(ldin % 4 == 0 && ldin >= Cin, "conv: ldin must be a multiple of 4 and >= Cin");
@@ -579,6 +598,11 @@ int ssp_conv_igemm_launch(const float* in, const float* wt, float* out, const fl
     a.bn_invstd = bnb->invstd; a.bn_slope = bnb->slope; a.bn_partial = bnb->partial;
     SSP_CHECK_ARG(bnb->nslot >= 1, "conv: the BatchNorm-backward partial buffer needs at least one row");
     a.bn_nslot = bnb->nslot;
+  }
+  if (adj) {
+    SSP_CHECK_ARG(R == 3 && ssp_wino_plan_tile(plan) && !ssp_wino_plan_fused(plan),
+                  "conv (adjoint data gradient): needs a through-memory Winograd plan (8xxxxxx / 9xxxxxx), got %d", plan);
+    return wino_launch(a, B, H, W, ws, ws_floats, plan, prof_kind, stream, true, dM);
   }
   if (ssp_wino_plan_fused(plan)) {
     a.ksplit = 1; a.ws = nullptr;

@@ -415,7 +415,10 @@ int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, in
 }
 int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                                int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream) {
-  if (tile == SSP_WINO_WGRAD_FUSED) return ssp_wino_wgrad_fused_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, ws, ws_floats, stream);
+  if (tile == SSP_WINO_WGRAD_FUSED) {
+    SSP_CHECK_ARG(dy != nullptr, "wgrad (Winograd, both transforms on the chip): dy must be given (no dM in memory to share)");
+    return ssp_wino_wgrad_fused_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, ws, ws_floats, stream);
+  }
   SSP_CHECK_ARG(tile == 2 || tile == 4, "wgrad (Winograd): tile must be 2, 4 or 12 (F(2x2) with both transforms on the chip)");
   SSP_CHECK_ARG(Cin % 16 == 0 && Cout % 16 == 0 && Cin >= 64 && Cout >= 64, "wgrad (Winograd): needs Cin, Cout >= 64 and %% 16 == 0");
   SSP_CHECK_ARG(ldx % 4 == 0 && ldx >= Cin && lddy % 4 == 0 && lddy >= Cout, "wgrad (Winograd): bad leading dimensions");
@@ -435,7 +438,10 @@ int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B
   // the region since
   if (x != nullptr)
     if (int rc = ssp_wino_input_launch(x, ldx, V, B, H, W, Cin, tile, SSP_PROF_WINO_WGRAD, stream)) return rc;
-  if (int rc = ssp_wino_outgrad_launch(dy, lddy, dM, B, H, W, Cout, tile, stream)) return rc;
+  // dy == nullptr: dM is already in its slot - ssp_wino_outgrad_transform_t put it there for the layer's adjoint data
+  // gradient (ssp_conv_dgrad_adj), which contracts the same planes
+  if (dy != nullptr)
+    if (int rc = ssp_wino_outgrad_launch(dy, lddy, dM, B, H, W, Cout, tile, stream)) return rc;
   const int r = ssp_conv_wgrad_dma_try(dM, V, dU, 1, 1, (int)T, Cin, Cout, Cout, Cin, 1, stream, P, T * Cout, T * Cin,
                                        (int64_t)Cout * Cin, 1);
   if (r < 0) return r;

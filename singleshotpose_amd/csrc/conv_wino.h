@@ -42,10 +42,14 @@ int ssp_wino_planes(int tile);
 int64_t ssp_wino_stat_groups(int B, int H, int W, int tile);
 // prof_kind: SSP_PROF_WINO_FWD / _DGRAD / _WGRAD - the family of the launch the pass belongs to
 int ssp_wino_input_launch(const float* in, int ldin, float* V, int B, int H, int W, int C, int tile, int prof_kind, hipStream_t stream);
-int ssp_wino_filter_launch(const float* w, float* U, int rows, int K, int tile, hipStream_t stream);
-int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, hipStream_t stream);
+// flip: w is the data-gradient layout (taps rotated by 180 degrees); U is the transform of the un-rotated filters
+int ssp_wino_filter_launch(const float* w, float* U, int rows, int K, int tile, hipStream_t stream, bool flip = false);
+int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, hipStream_t stream,
+                            int prof_kind = SSP_PROF_WINO_WGRAD);
 int ssp_wino_wgrad_finish_launch(const float* dU, float* dw, int rows, int K, int tile, hipStream_t stream);
-int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, int prof_kind, hipStream_t stream);
+// adj: the planes are dV of the adjoint data gradient (B dV B^T gathered over the neighbouring tiles) instead of M (A^T M A)
+int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, int prof_kind, hipStream_t stream,
+                           bool adj = false);
 
 // on-chip F(2x2) (conv_wino_fused.hip); `a` = the conv launch's ConvArgs (struct ConvArgs, conv_igemm_common.h)
 struct ConvArgs;

@@ -18,6 +18,9 @@
 //     per-tile-group BatchNorm statistics, fused BatchNorm-backward reductions);
 //   * wino_outgrad_kernel  dM = A dY A^T and wino_wgrad_finish_kernel  dw += G^T dU G  for the filter gradient, which is the
 //     same P-fold batched launch of the LDS-direct filter-gradient kernel over the tiles.
+//   * wino_dgrad_finish_kernel  the data gradient as the ADJOINT of the forward map, from the filter gradient's dM and the
+//     forward filter transform with the channels transposed (wino_filter_kernel<n, true>): dX = overlap-add of B dV B^T,
+//     gathered per tile; wino_output_kernel's epilogue (wino_form_adjoint below).
 //
 // n = 2 uses the points (0, 1, -1): constants 1, -1, 1/2 only; result within ~1e-6 of the direct kernel.
 // n = 4 uses the points (0, 1, -1, 1/2, -2) - NOT the textbook (0, +-1, +-2): on this network's operand statistics the
@@ -188,7 +191,9 @@ __global__ void __launch_bounds__(256) wino_input_kernel(const float* __restrict
 }
 
 // ---- U[xi][row][k] = (G g G^T)[xi] of the 3x3 filter g[tap] = w[row][tap][k]; thread = (row, 4 k's) ---------------------
-template <int N>
+// FLIP: g[tap] = w[row][8 - tap][k] - the transform of the UN-flipped filter out of the data-gradient layout, whose taps are
+// stored rotated by 180 degrees: the operand of the adjoint data gradient (wino_dgrad_finish_kernel below)
+template <int N, bool FLIP = false>
 __global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restrict__ w, float* __restrict__ U, int rows, int K) {
   constexpr int A = N + 2;
   using M_ = WinoMat<N>;
@@ -202,7 +207,7 @@ __global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restric
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) g[i][j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(i * 3 + j) * K);
+    for (int j = 0; j < 3; ++j) g[i][j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(FLIP ? 8 - (i * 3 + j) : i * 3 + j) * K);
   f32x4 h[A][3];      // G g
   ssp_sfor<A>([&](auto I) {
     constexpr int i = decltype(I)::value;
@@ -240,12 +245,117 @@ __global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restric
 // odd edges make it vary) behind the pairs: stats [groups][Cout][2] | counts [groups] - bn_fwd_finalize's counted format.
 // CS = channel quads per workgroup (16: a 64-channel slab, 16 tiles side by side; 64: a 256-channel slab, 4 tiles side by
 // side, the group's 16 tiles in 4 passes): a tile row of the slab is one contiguous piece of a plane - 256 bytes or 1 KiB.
-template <int N, int CS>
-__global__ void __launch_bounds__(256) wino_output_kernel(WinoOutArgs p, WinoGeom g) {
+// Y = A^T M A of one tile; src = plane 0 of the tile's 4 channels
+template <int N>
+__device__ __forceinline__ void wino_form_output(f32x4 (&Y)[N][N], const float* __restrict__ src, const int64_t plane) {
   constexpr int A = N + 2;
+  using M_ = WinoMat<N>;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  // row i of the transform domain at a time: rr = M[i][:] A (n values), then Y[:][q] += A^T[:][i] rr[q]
+  ssp_sfor<A>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    f32x4 m[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) m[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(i * A + j) * plane);
+    ssp_sfor<N>([&](auto Q) {
+      constexpr int qq = decltype(Q)::value;
+      f32x4 rr = z4;
+      ssp_sfor<A>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        { constexpr float cc_ = M_::AT[qq][j]; wino_mad(rr, cc_, m[j]); }
+      });
+      ssp_sfor<N>([&](auto Pp) {
+        constexpr int pp = decltype(Pp)::value;
+        { constexpr float cc_ = M_::AT[pp][i]; wino_mad(Y[pp][qq], cc_, rr); }
+      });
+    });
+  });
+}
+
+// The data gradient as the ADJOINT of the forward map: the planes hold dV_xi[t][ci] = sum_co dM_xi[t][co] U_xi[co][ci]
+// (dM = A dY A^T, the filter gradient's transformed output gradient; U the forward filter transform), a tile's contribution
+// to dX is the (n+2) x (n+2) window dd = B dV B^T (B = (B^T)^T) at the tile's input window, and dX is the overlap-add of
+// the windows.  Gathered per n x n tile: rows / columns 1..n of the tile's own window, plus row n+1 of the tile above,
+// row 0 of the tile below, column n+1 of the left tile, column 0 of the right one and one corner value of each diagonal
+// neighbour.  Columns 0 and n+1 of B^T are unit vectors (the points 0 and infinity; tests/test_wino_adjoint_cpu.py pins
+// it), so a neighbour's edge row depends on ONE row of its planes: 4 (n+2) + 4 extra values per thread, read from planes
+// the neighbouring threads read anyway.  A neighbour outside [0, th) x [0, tw) does not exist - its planes are never
+// addressed; inside a mosaic the windows straddle the gap row / column like the forward ones.
+template <int N>
+__device__ __forceinline__ void wino_form_adjoint(f32x4 (&Y)[N][N], const float* __restrict__ src, const int64_t plane,
+                                                  const int C, const WinoGeom& g, const int ty, const int tx) {
+  constexpr int A = N + 2;
+  using M_ = WinoMat<N>;
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  constexpr float c0 = M_::BT[0][0], cl = M_::BT[A - 1][A - 1];      // the one non-zero of column 0 / column n+1 of B^T
+  constexpr float c00 = c0 * c0, c0l = c0 * cl, cll = cl * cl;
+  // own window: row i of the planes at a time, rr[q] = sum_j dV[i][j] B^T[j][q+1], Y[p][q] += B^T[i][p+1] rr[q]
+  ssp_sfor<A>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    f32x4 m[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) m[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(i * A + j) * plane);
+    ssp_sfor<N>([&](auto Q) {
+      constexpr int qq = decltype(Q)::value;
+      f32x4 rr = z4;
+      ssp_sfor<A>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        { constexpr float cc_ = M_::BT[j][qq + 1]; wino_mad(rr, cc_, m[j]); }
+      });
+      ssp_sfor<N>([&](auto Pp) {
+        constexpr int pp = decltype(Pp)::value;
+        { constexpr float cc_ = M_::BT[i][pp + 1]; wino_mad(Y[pp][qq], cc_, rr); }
+      });
+    });
+  });
+  const bool up = ty > 0, dn = ty + 1 < g.th, lf = tx > 0, rt = tx + 1 < g.tw;
+  const int64_t trow = (int64_t)g.tw * C;      // one tile row further in a plane
+  // (vertical neighbour: plane row `PR` of it, into output row `OR`; its left / right neighbours give the corners)
+  auto vertical = [&](const float* __restrict__ s, auto PR, auto OR, const float ce, const float cleft, const float cright) {
+    constexpr int pr = decltype(PR)::value, orow = decltype(OR)::value;
+    f32x4 m[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) m[j] = *reinterpret_cast<const f32x4*>(s + (int64_t)(pr * A + j) * plane);
+    ssp_sfor<N>([&](auto Q) {
+      constexpr int qq = decltype(Q)::value;
+      f32x4 rr = z4;
+      ssp_sfor<A>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        { constexpr float cc_ = M_::BT[j][qq + 1]; wino_mad(rr, cc_, m[j]); }
+      });
+      wino_mad(Y[orow][qq], ce, rr);
+    });
+    if (lf) wino_mad(Y[orow][0], cleft, *reinterpret_cast<const f32x4*>(s - C + (int64_t)(pr * A + A - 1) * plane));
+    if (rt) wino_mad(Y[orow][N - 1], cright, *reinterpret_cast<const f32x4*>(s + C + (int64_t)(pr * A) * plane));
+  };
+  if (up) vertical(src - trow, std::integral_constant<int, A - 1>{}, std::integral_constant<int, 0>{}, cl, cll, c0l);
+  if (dn) vertical(src + trow, std::integral_constant<int, 0>{}, std::integral_constant<int, N - 1>{}, c0, c0l, c00);
+  // (horizontal neighbour: plane column `PC` of it, into output column `OC`)
+  auto horizontal = [&](const float* __restrict__ s, auto PC, auto OC, const float ce) {
+    constexpr int pc = decltype(PC)::value, ocol = decltype(OC)::value;
+    f32x4 m[A];
+#pragma unroll
+    for (int i = 0; i < A; ++i) m[i] = *reinterpret_cast<const f32x4*>(s + (int64_t)(i * A + pc) * plane);
+    ssp_sfor<N>([&](auto Pp) {
+      constexpr int pp = decltype(Pp)::value;
+      f32x4 rr = z4;
+      ssp_sfor<A>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        { constexpr float cc_ = M_::BT[i][pp + 1]; wino_mad(rr, cc_, m[i]); }
+      });
+      wino_mad(Y[pp][ocol], ce, rr);
+    });
+  };
+  if (lf) horizontal(src - C, std::integral_constant<int, A - 1>{}, std::integral_constant<int, 0>{}, cl);
+  if (rt) horizontal(src + C, std::integral_constant<int, 0>{}, std::integral_constant<int, N - 1>{}, c0);
+}
+
+// ADJ: the n x n values are the adjoint data gradient's (wino_form_adjoint); everything from "the tile's valid pixels" on
+// is the same code
+template <int N, int CS, bool ADJ>
+__device__ __forceinline__ void wino_finish_body(const WinoOutArgs& p, const WinoGeom& g) {
   constexpr int TP = 256 / CS;                 // tiles per pass
   constexpr int NP = SSP_WINO_TG / TP;         // passes over the group
-  using M_ = WinoMat<N>;
   const int tid = threadIdx.x, gl = tid % CS, tl = tid / CS;
   const int c = blockIdx.y * (CS * 4) + gl * 4;
   const bool cok = c < p.Cout;                 // Cout % 4 == 0 on this path (checked by the launcher)
@@ -280,25 +390,8 @@ __global__ void __launch_bounds__(256) wino_output_kernel(WinoOutArgs p, WinoGeo
     const int ty = (int)(q - (unsigned)mb * (unsigned)g.th);
     const float* src = p.Mw + t64 * p.Cout + c;
     const int64_t plane = g.T * p.Cout;
-    // row i of the transform domain at a time: rr = M[i][:] A (n values), then Y[:][q] += A^T[:][i] rr[q]
-    ssp_sfor<A>([&](auto I) {
-      constexpr int i = decltype(I)::value;
-      f32x4 m[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) m[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(i * A + j) * plane);
-      ssp_sfor<N>([&](auto Q) {
-        constexpr int qq = decltype(Q)::value;
-        f32x4 rr = z4;
-        ssp_sfor<A>([&](auto J) {
-          constexpr int j = decltype(J)::value;
-          { constexpr float cc_ = M_::AT[qq][j]; wino_mad(rr, cc_, m[j]); }
-        });
-        ssp_sfor<N>([&](auto Pp) {
-          constexpr int pp = decltype(Pp)::value;
-          { constexpr float cc_ = M_::AT[pp][i]; wino_mad(Y[pp][qq], cc_, rr); }
-        });
-      });
-    });
+    if constexpr (ADJ) wino_form_adjoint<N>(Y, src, plane, p.Cout, g, ty, tx);
+    else wino_form_output<N>(Y, src, plane);
     // the tile's valid pixels: epilogue + statistics of the raw (bias-free) values (count and mean, then M2)
     float cnt = 0.f;
     f32x4 sum = z4;
@@ -403,6 +496,23 @@ __global__ void __launch_bounds__(256) wino_output_kernel(WinoOutArgs p, WinoGeo
       if (ch == 0) p.stats[(int64_t)gridDim.x * p.Cout * 2 + blockIdx.x] = n_;      // the group's pixel count
     }
   }
+}
+
+template <int N, int CS>
+__global__ void __launch_bounds__(256) wino_output_kernel(WinoOutArgs p, WinoGeom g) {
+  wino_finish_body<N, CS, false>(p, g);
+}
+// finishing pass of the adjoint data gradient (ssp_conv_dgrad_adj): same grid, same thread = (tile, 4 channels)
+// (64-channel slabs: two waves per SIMD, as wino_output_kernel<4, 16> gets by itself - left alone the F(4x4) instance is
+// allocated ten registers past the 256 of that occupancy, for the neighbour flags and offsets; held to 256 it parks nine
+// values in scratch: 275 -> 265 us per launch in the step.  The wide experiment instances keep the allocator's choice.
+// The pass still takes twice the forward one's time: the neighbour reads sit behind their guards, one memory latency each.
+// Tried: XCD-contiguous workgroup order (nothing), unconditional reads through pointers clamped to the own tile (all 64
+// loads in flight: 150 spilled values per lane) - DESIGN.md section 3a.)
+template <int N, int CS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CS == 16 ? 2 : 1)))
+wino_dgrad_finish_kernel(WinoOutArgs p, WinoGeom g) {
+  wino_finish_body<N, CS, true>(p, g);
 }
 
 // ---- filter gradient in the transform domain --------------------------------------------------------------------------
@@ -526,7 +636,8 @@ int64_t ssp_wino_tiles(int B, int H, int W, int tile) { return wino_geom(B, H, W
 int ssp_wino_planes(int tile) { return (tile + 2) * (tile + 2); }
 int64_t ssp_wino_stat_groups(int B, int H, int W, int tile) { return (ssp_wino_tiles(B, H, W, tile) + SSP_WINO_TG - 1) / SSP_WINO_TG; }
 
-int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, hipStream_t stream) {
+int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, hipStream_t stream,
+                            int prof_kind) {
   SSP_CHECK_ARG(wino_tile_ok(tile), "wino_outgrad: tile must be 2 or 4");
   const WinoGeom g = wino_geom(B, H, W, tile);
   const int wv = ssp_option(SSP_OPT_WINO_VARIANT);      // experiments: bit 0 = 4 channels per thread at F(4x4), bit 1 = non-temporal stores
@@ -535,7 +646,7 @@ int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, 
                 "wino_outgrad: channels must be a multiple of 4 and the operands 16-byte aligned");
   SSP_CHECK_ARG(g.T * (C / cv) < (1ll << 31), "wino_outgrad: too many (tile, channel) pairs");
   const int P = ssp_wino_planes(tile);
-  SspProfScope prof(SSP_PROF_WINO_WGRAD, stream, 4.0 * C * ((double)B * H * W + (double)P * g.T));
+  SspProfScope prof(prof_kind, stream, 4.0 * C * ((double)B * H * W + (double)P * g.T));
   const int64_t n = g.T * (C / cv);
   const SspFastDiv dc = ssp_fastdiv((unsigned)(C / cv));
   const dim3 grid((unsigned)((n + 255) / 256));
@@ -582,21 +693,25 @@ int ssp_wino_input_launch(const float* in, int ldin, float* V, int B, int H, int
   return SSP_OK;
 }
 
-int ssp_wino_filter_launch(const float* w, float* U, int rows, int K, int tile, hipStream_t stream) {
+int ssp_wino_filter_launch(const float* w, float* U, int rows, int K, int tile, hipStream_t stream, bool flip) {
   SSP_CHECK_ARG(wino_tile_ok(tile), "wino_filter: tile must be 2 or 4");
   SSP_CHECK_ARG(w != nullptr && U != nullptr && rows > 0 && K > 0 && K % 4 == 0 && (((uintptr_t)w) & 15) == 0 &&
                     (((uintptr_t)U) & 15) == 0,
                 "wino_filter: [rows][9][K] filters with K % 4 == 0, 16-byte aligned operands");
   SspProfScope prof(SSP_PROF_LAYOUT, stream, 4.0 * (9.0 + ssp_wino_planes(tile)) * (double)rows * K);
   const int64_t n = (int64_t)rows * (K / 4);
-  if (tile == 2) hipLaunchKernelGGL(wino_filter_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, U, rows, K);
-  else hipLaunchKernelGGL(wino_filter_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, U, rows, K);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (tile == 2 && flip) hipLaunchKernelGGL((wino_filter_kernel<2, true>), grid, dim3(256), 0, stream, w, U, rows, K);
+  else if (tile == 2) hipLaunchKernelGGL((wino_filter_kernel<2>), grid, dim3(256), 0, stream, w, U, rows, K);
+  else if (flip) hipLaunchKernelGGL((wino_filter_kernel<4, true>), grid, dim3(256), 0, stream, w, U, rows, K);
+  else hipLaunchKernelGGL((wino_filter_kernel<4>), grid, dim3(256), 0, stream, w, U, rows, K);
   SSP_CHECK_LAUNCH("wino_filter");
   return SSP_OK;
 }
 
 // the finishing pass; `a` = the conv launch's own arguments (conv_igemm.hip fills a WinoOutArgs from its ConvArgs)
-int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, int prof_kind, hipStream_t stream) {
+// adj: a.Mw holds the adjoint data gradient's planes dV (wino_dgrad_finish_kernel)
+int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, int prof_kind, hipStream_t stream, bool adj) {
   SSP_CHECK_ARG(wino_tile_ok(tile), "wino_output: tile must be 2 or 4");
   const WinoGeom g = wino_geom(B, H, W, tile);
   const int P = ssp_wino_planes(tile);
@@ -605,6 +720,14 @@ int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, 
   // any layer and 5-10 % worse on the 52 x 52 / 26 x 26 ones (profiles/r04_wino_xform_variants.txt): experiment switch only
   const bool wide = a.Cout >= 256 && (ssp_option(SSP_OPT_WINO_VARIANT) & 4);
   const dim3 grid((unsigned)((g.T + SSP_WINO_TG - 1) / SSP_WINO_TG), (unsigned)ssp_cdiv(a.Cout, wide ? 256 : 64));
+  if (adj) {
+    if (tile == 2 && wide) hipLaunchKernelGGL((wino_dgrad_finish_kernel<2, 64>), grid, dim3(256), 0, stream, a, g);
+    else if (tile == 2) hipLaunchKernelGGL((wino_dgrad_finish_kernel<2, 16>), grid, dim3(256), 0, stream, a, g);
+    else if (wide) hipLaunchKernelGGL((wino_dgrad_finish_kernel<4, 64>), grid, dim3(256), 0, stream, a, g);
+    else hipLaunchKernelGGL((wino_dgrad_finish_kernel<4, 16>), grid, dim3(256), 0, stream, a, g);
+    SSP_CHECK_LAUNCH("wino_dgrad_finish");
+    return SSP_OK;
+  }
   if (tile == 2 && wide) hipLaunchKernelGGL((wino_output_kernel<2, 64>), grid, dim3(256), 0, stream, a, g);
   else if (tile == 2) hipLaunchKernelGGL((wino_output_kernel<2, 16>), grid, dim3(256), 0, stream, a, g);
   else if (wide) hipLaunchKernelGGL((wino_output_kernel<4, 64>), grid, dim3(256), 0, stream, a, g);

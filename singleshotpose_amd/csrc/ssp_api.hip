@@ -13,8 +13,10 @@ int64_t ssp_conv_ws_floats(int M, int Cin, int Cout, int R, int plan);
 int ssp_conv_igemm_launch(const float* in, const float* wt, float* out, const float* bias, float* stats, int B, int H,
                           int W, int Cin, int Cout, int ldin, int ldout, int R, int accumulate, float* ws,
                           int64_t ws_floats, int plan, int prof_kind, hipStream_t stream,
-                          const float* escale = nullptr, float act_slope = 1.f, const SspBnBwdFuse* bnb = nullptr);
+                          const float* escale = nullptr, float act_slope = 1.f, const SspBnBwdFuse* bnb = nullptr,
+                          bool adj = false, const float* dM = nullptr);
 int64_t ssp_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile);
+int64_t ssp_wino_adj_ws_floats(int B, int H, int W, int Cout_dy, int Cin_dx, int tile, bool own_dm);
 int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                           int ldx, int R, hipStream_t stream);
 int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile);
@@ -270,6 +272,38 @@ int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int
   }
   return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, 0, workspace,
                                workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f, &f);
+}
+// ---- the data gradient as the adjoint of the Winograd forward map (conv_wino.hip wino_dgrad_finish_kernel) ----
+int ssp_wino_outgrad_transform_t(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, void* stream) {
+  return ssp_wino_outgrad_launch(dy, lddy, dM, B, H, W, C, tile, (hipStream_t)stream, SSP_PROF_WINO_DGRAD);
+}
+int ssp_wino_filter_transform_adj_t(const float* w9d, float* Ut, int rows, int K, int tile, void* stream) {
+  return ssp_wino_filter_launch(w9d, Ut, rows, K, tile, (hipStream_t)stream, true);
+}
+int64_t ssp_conv_dgrad_adj_workspace_floats(int B, int H, int W, int Cout_dy, int Cin_dx, int plan, int own_dm) {
+  const int tile = ssp_wino_plan_tile(plan);
+  if (!tile || ssp_wino_plan_fused(plan)) return 0;
+  return ssp_wino_adj_ws_floats(B, H, W, Cout_dy, Cin_dx, tile, own_dm != 0);
+}
+int ssp_conv_dgrad_adj(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                       int lddx, int R, int accumulate, int plan, float* workspace, int64_t workspace_floats,
+                       const float* dM, void* stream) {
+  return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, accumulate,
+                               workspace, workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f,
+                               nullptr, true, dM);
+}
+int ssp_conv_dgrad_adj_bnbwd(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
+                             int lddy, int lddx, int R, int plan, float* workspace, int64_t workspace_floats,
+                             const float* raw, int ldraw, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, float slope, float* partial, int partial_rows, const float* dM,
+                             void* stream) {
+  SspBnBwdFuse f = {raw, ldraw, scale, shift, mean, invstd, slope, partial, partial_rows};
+  if (partial == nullptr) {
+    ssp_set_error("conv_dgrad_adj_bnbwd: partial must not be NULL (use ssp_conv_dgrad_adj)");
+    return SSP_ERR_ARG;
+  }
+  return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, 0, workspace,
+                               workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f, &f, true, dM);
 }
 int ssp_bn_act_bwd_partials(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
                             const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W,

@@ -45,6 +45,13 @@ IGEMM_LATENCY_CANDS = (6418, 12818, 6428, 12828, 6438)
 WINO_GEMM_CANDS = (6413, 6414, 12813, 12814)
 
 
+# A layer whose data gradient AND filter gradient both run in the through-memory Winograd domain of one tile size takes the
+# data gradient in its adjoint form (ssp_conv_dgrad_adj): it contracts the dM = A dY A^T planes the filter gradient
+# transforms dY into anyway, so dY is transformed once per step instead of twice.  A rule of the plan, like the shared V -
+# not a tuner choice, no plan code, not part of the tune tag.  SSP_WINO_SHARE_DM=0 (read once) switches it off for A/Bs.
+_SHARE_DM = os.environ.get('SSP_WINO_SHARE_DM', '1') != '0'
+
+
 def _tune_tag():
     """Candidate-set tag, part of every tune-cache key: a cache entry written before a family of candidates existed, or in a
     process that had it switched off (SSP_WINOGRAD=0, SSP_WINO_TILES, SSP_WINO_MIN_CHANNELS), must not keep that family
@@ -267,6 +274,7 @@ class _ConvSpec(object):
     wino_u = wino_ud = None        # {tile: Winograd-transformed forward / data-gradient filters}
     wino_ws = wino_ws_floats = None    # per-layer workspace of a Winograd filter gradient, and its size
     wgrad_wino = 0                 # filter gradient: 0 = direct, else the Winograd tile (or WGRAD_FUSED)
+    dgrad_adj = False              # data gradient in the adjoint form, from the filter gradient's dM (_adjoint_rule)
     ws_dgrad = 0                   # split-K workspace floats of the data-gradient plan
     fwd_fams = None                # {family: (code, ms)} the head-error budget chooses from
     stats = None                   # per-tile BatchNorm partial statistics
@@ -893,6 +901,16 @@ class Plan(object):
         self._plan_bn_fusion()
         self._fit_workspace()
 
+    def _adjoint_rule(self, cs):
+        """Whether the layer takes the adjoint form of the data gradient (see _SHARE_DM): its data-gradient plan is a
+        through-memory Winograd code of tile n, its filter gradient runs at the same tile, and dY has no padding channels
+        (the filter gradient's dM [P][T][cout] is then the data gradient's operand [P][T][coutp]).  A function of the
+        layer's plan codes alone; applied where the layer's data-gradient operand is prepared (_repack_dgrad), so the
+        operand and the launch that reads it always agree."""
+        t = wino_tile(cs.plan_dgrad)
+        return bool(_SHARE_DM and not cs.first and t and not wino_fused(cs.plan_dgrad) and cs.wgrad_wino == t and
+                    cs.coutp == cs.cout)
+
     def _wgrad_key(self, cs):
         return ('wgrad', self.B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw, cs.inp.ld, _tune_tag())
 
@@ -1052,9 +1070,12 @@ class Plan(object):
         _lib.call('ssp_repack_dgrad_packed' if cs.packed else 'ssp_repack_dgrad', src.data_ptr(),
                   _ptr(self._dpack, cs.doff), cs.cout, cs.cin, cs.coutp, cs.k, stream.cuda_stream)
         tile = wino_tile(cs.plan_dgrad)
+        cs.dgrad_adj = self._adjoint_rule(cs)
         if tile:      # Winograd data-gradient plan: its filter operand is the transform of that layout
-            _lib.call('ssp_wino_filter_transform_t', _ptr(self._dpack, cs.doff), self._wino_ud(cs, tile).data_ptr(), cs.cin,
-                      cs.coutp, tile, stream.cuda_stream)
+            # (adjoint form: of the same layout with the taps read back to front - the forward transform, channels transposed)
+            _lib.call('ssp_wino_filter_transform_adj_t' if cs.dgrad_adj else 'ssp_wino_filter_transform_t',
+                      _ptr(self._dpack, cs.doff), self._wino_ud(cs, tile).data_ptr(), cs.cin, cs.coutp, tile,
+                      stream.cuda_stream)
 
     # ------------------------------------------------------------------ per-shape tile / split selection
     def _autotune(self, which):
@@ -1722,26 +1743,28 @@ class Plan(object):
             self.grads[ind] = g
         return g
 
-    def _dgrad(self, cs, src, dy_ptr, dy_ld, written, fused_stats, st, fold=True):
+    def _dgrad(self, cs, src, dy_ptr, dy_ld, written, fused_stats, st, fold=True, dm_ptr=None):
         """Data gradient of conv block `cs` into the gradient buffer of its input's producer `src` (with the producer's
-        BatchNorm-backward sums folded in where _plan_bn_fusion arranged it)."""
+        BatchNorm-backward sums folded in where _plan_bn_fusion arranged it).  dm_ptr: a layer in the adjoint form
+        (cs.dgrad_adj) whose dM = A dY A^T is already in memory; None there = the launch transforms dY itself."""
         call = _lib.call
         B = self.B
         gin = self._grad_buf(src, cs.inp)
         scs = cs.bn_fuse_src
         dwt = (self._wino_ud(cs, wino_tile(cs.plan_dgrad)).data_ptr() if wino_tile(cs.plan_dgrad)
                else _ptr(self._dpack, cs.doff))
+        adj = (dm_ptr, st) if cs.dgrad_adj else (st,)
         if scs is not None and fold and src not in written:
             sv = scs.vec
-            call('ssp_conv_dgrad_bnbwd', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W,
+            call('ssp_conv_dgrad_adj_bnbwd' if cs.dgrad_adj else 'ssp_conv_dgrad_bnbwd', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W,
                  cs.coutp, cs.cin, dy_ld, gin.ld, cs.k, cs.plan_dgrad, self.ws.data_ptr(), self.ws_floats,
                  scs.raw.data_ptr(), scs.ldraw, sv[2].data_ptr(), sv[3].data_ptr(), sv[0].data_ptr(),
-                 sv[1].data_ptr(), scs.slope, scs.bnp[0].data_ptr(), scs.bnp[1], st)
+                 sv[1].data_ptr(), scs.slope, scs.bnp[0].data_ptr(), scs.bnp[1], *adj)
             fused_stats.add(src)
         else:
-            call('ssp_conv_dgrad', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W, cs.coutp,
+            call('ssp_conv_dgrad_adj' if cs.dgrad_adj else 'ssp_conv_dgrad', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W, cs.coutp,
                  cs.cin, dy_ld, gin.ld, cs.k, 1 if src in written else 0, cs.plan_dgrad, self.ws.data_ptr(),
-                 self.ws_floats, st)
+                 self.ws_floats, *adj)
         written.add(src)
 
     def backward(self, grad_out, want_input=False, want_params=True):
@@ -2004,16 +2027,26 @@ class Plan(object):
         # chain that ends the step - BEFORE its filter gradient is released on the side stream
         owner = None if src is None else (self.convs.get(src - 1) if src in self.fused_pool else self.convs.get(src))
         defer = params and tail_sched and owner is not None and owner.first_live and s.dgrad[0]
+        # adjoint-form layer whose filter gradient runs too: dY is transformed ONCE, on the main stream, into the dM slot
+        # of the layer's filter-gradient workspace - both gradients contract those planes.  (No filter gradient in this
+        # schedule - frozen parameters, input-only backward: the data-gradient launch transforms dY into its own workspace.)
+        dm_ptr = None
+        if cs.dgrad_adj and s.dgrad[0] and s.wgrad and cs.packed and cs.wgrad_wino:
+            t = cs.wgrad_wino        # V [P][T][cinp] | dM | dU (csrc/conv_wgrad.hip)
+            dm_ptr = _ptr(self._wino_ws(cs), (t + 2) ** 2 * _lib.query('ssp_conv_wino_tiles', B, cs.H, cs.W, t) * cs.cinp)
+            call('ssp_wino_outgrad_transform_t', dy_ptr, dy_ld, dm_ptr, B, cs.H, cs.W, cs.cout, cs.wgrad_wino, st)
         if defer:
-            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn)
+            self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn, dm_ptr)
         if params:
             side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
         if s.wgrad:
             gw = gview(cs.conv.weight, cs.packed)
             if cs.packed and cs.wgrad_wino:
                 wws = self._wino_ws(cs)
-                call('ssp_conv_wgrad_wino_t', dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(),
-                     B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(), wws.numel(), st2)
+                # (dy = NULL: dM is in its slot of wws already, see above)
+                call('ssp_conv_wgrad_wino_t', None if dm_ptr is not None else dy_ptr, None if cs.v_live else cs.inp.ptr,
+                     gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(),
+                     wws.numel(), st2)
                 cs.v_live = False
             elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
                 call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
@@ -2030,7 +2063,7 @@ class Plan(object):
             if cs.first:
                 self._input_dgrad(cs, dy_ptr, dy_ld, written, st)
             else:
-                self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn)
+                self._dgrad(cs, src, dy_ptr, dy_ld, written, fused_stats, st, s.fold_bn, dm_ptr)
 
     def _input_gbuf(self, written):
         """The input's gradient buffer, NHWC [B*H*W][in_cp], and whether a launch accumulates into it (marks it written)."""
