@@ -117,9 +117,11 @@ int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int
  * into anyway - with the FORWARD filter transform, channels transposed; no B^T dY B planes and no second transform of dY.
  * Same result as the data gradient entry points above with the same plan, to fp32 rounding (~5e-6 of the range at tile 4).
  *   ssp_wino_outgrad_transform_t: dM [(tile+2)^2][tiles][C] = A dY A^T of dy [B*H*W][lddy], tile 2 or 4, C % 4 == 0; timed
- *     with the Winograd data-gradient family.  Into the dM slot of a filter-gradient workspace (V | dM | dU: offset
- *     (tile+2)^2 * tiles * Cin floats) it feeds BOTH gradients: ssp_conv_wgrad_wino_t then takes dy == NULL (tiles 2 and 4
- *     only; tile 12 keeps dM on the chip and refuses it).
+ *     with the Winograd data-gradient family.  Into the dM slot of a filter-gradient workspace (V | dM | dU: V
+ *     [(tile+2)^2][tiles][Cin] at the head, dM [(tile+2)^2][tiles][Cout] at offset (tile+2)^2 * tiles * Cin floats, dU
+ *     [(tile+2)^2][Cout][Cin] - the transform-domain filter gradient sum_t dM[t][co] * V[t][ci] that G^T dU G turns into dw,
+ *     left there by the launch - at offset (tile+2)^2 * tiles * (Cin + Cout)) it feeds BOTH gradients: ssp_conv_wgrad_wino_t
+ *     then takes dy == NULL (tiles 2 and 4 only; tile 12 keeps dM on the chip and refuses it).
  *   ssp_wino_filter_transform_adj_t: Ut[xi][row][k] = (G g G^T)[xi] of the UN-flipped filters out of the data-gradient
  *     layout w9d [rows = Cin_dx][tap][K = Cout_dy] (ssp_repack_dgrad, whose taps are rotated by 180 degrees): bit for bit
  *     the forward transform of the same filters packed [Cin_dx][tap][Cout_dy] without the rotation.
