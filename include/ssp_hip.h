@@ -184,6 +184,40 @@ int64_t ssp_conv_wgrad_wino_workspace_floats(int B, int H, int W, int Cin, int C
 int ssp_conv_wgrad_wino(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                         int ldx, float* workspace, int64_t workspace_floats, void* stream);
 
+/* ---- stride-2 convolution (appended to ABI 5; csrc/conv_strided.hip): nn.Conv2d(Cin, Cout, R, stride 2, padding R/2) at
+ * darknet.py:156,160 with stride = 2, R = 1 or 3, exact fp32 on the matrix cores, any position of a net but the first
+ * block.  H, W are ALWAYS the sizes of the block's INPUT map; the output map is Ho x Wo, Ho = (H + 2*(R/2) - R)/2 + 1 (odd
+ * and even H both), input row of output row yo and tap r = 2*yo + r - R/2, zero outside the map.  No plan codes, no
+ * workspace.  Limits of all three: Cin % 4 == 0 (data gradient: Cout_dy % 4 == 0, the padded width of dy), leading dimensions
+ * % 4 == 0 and >= the channel counts, 16-byte aligned operands, B*H*W < 2^31; anything else is SSP_ERR_ARG with a message
+ * and nothing is launched.
+ *   forward: out[po][co] (+)= sum_{tap,ci} in[gather(po, tap)][ci] * wt[co][tap][ci] (+ bias[co]) over the B*Ho*Wo output
+ *     pixels; wt from ssp_repack_fwd.  stats (nullable, not with accumulate): per-tile (mean, M2) pairs of the raw output,
+ *     [ssp_conv_s2_stats_tiles][Cout][2], tiles of ssp_conv_s2_stats_tile_m output pixels (64 or 128, the last tile
+ *     partial): ssp_bn_fwd_finalize takes them with that tile_m and M = B*Ho*Wo.  The _affine form is the eval-mode block
+ *     in one launch, out = leaky(scale[co] * conv + shift[co], slope), as ssp_conv_fwd_affine.
+ *   data gradient: dx[pi][ci] (+)= sum over the (output pixel, tap) pairs that read input pixel pi of dy[po][co] *
+ *     w[co][ci][tap]; wt from ssp_repack_dgrad (Coutp = Cout_dy).  One launch, decomposed by the parity of pi = (yi, xi):
+ *     at R = 3 an even coordinate is reached by tap 1 only, an odd one by taps 0 and 2, so the four classes contract 1, 2,
+ *     2 and 4 taps (9/4 per pixel on average, never nine masked ones); at R = 1 only (even, even) pixels receive anything,
+ *     the others are written as zeros (accumulate = 0) or left untouched (accumulate = 1).  Every pixel of dx's Cin_dx
+ *     columns is written by exactly one thread (deterministic) - except on grids of fewer than 512 workgroups (3x3), which
+ *     hand every (class, tap) pair to workgroups of its own and sum a pixel's taps with fp32 atomic adds (dx zeroed first
+ *     when accumulate = 0): the same sum in an order that may differ from run to run.  Columns >= Cin_dx of a wider lddx are
+ *     not touched.
+ *   filter gradient: dw[co][tap][ci] += sum_po dy[po][co] * in[gather(po, tap)][ci], [Cout][R*R][Cin] packed, zeroed by
+ *     the caller (the pixel reduction is split over workgroups and summed with fp32 atomics), as ssp_conv_wgrad. */
+int ssp_conv_s2_fwd(const float* in, const float* wt, float* out, const float* bias, float* stats, int B, int H, int W,
+                    int Cin, int Cout, int ldin, int ldout, int R, int accumulate, void* stream);
+int ssp_conv_s2_fwd_affine(const float* in, const float* wt, float* out, const float* scale, const float* shift, float slope,
+                           int B, int H, int W, int Cin, int Cout, int ldin, int ldout, int R, void* stream);
+int ssp_conv_s2_stats_tile_m(int B, int H, int W, int Cin, int Cout, int R);
+int ssp_conv_s2_stats_tiles(int B, int H, int W, int Cin, int Cout, int R);
+int ssp_conv_s2_dgrad(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                      int lddx, int R, int accumulate, void* stream);
+int ssp_conv_s2_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy, int ldx,
+                      int R, void* stream);
+
 /* ---- BatchNorm2d(eps) + LeakyReLU(slope) (+ 2x2/2 max-pool): darknet.py:157,162,172 ------------------------- */
 /* stats: `ntile` per-tile (mean, M2) pairs per channel from a conv launch; tile_m = its ssp_conv_stats_tile_m (rows per
  * tile; the last tile holds M - (ntile-1)*tile_m), or 0 = counted format (the tiles' pixel counts follow the pairs) */

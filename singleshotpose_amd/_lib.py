@@ -44,6 +44,12 @@ _SIGS = {
     "ssp_conv_dgrad_adj_workspace_floats": [I, I, I, I, I, I, I],
     "ssp_conv_dgrad_adj": [P, P, P, I, I, I, I, I, I, I, I, I, I, P, L, P, P],
     "ssp_conv_dgrad_adj_bnbwd": [P, P, P, I, I, I, I, I, I, I, I, I, P, L, P, I, P, P, P, P, F, P, I, P, P],
+    "ssp_conv_s2_fwd": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],
+    "ssp_conv_s2_fwd_affine": [P, P, P, P, P, F, I, I, I, I, I, I, I, I, P],
+    "ssp_conv_s2_stats_tile_m": [I, I, I, I, I, I],
+    "ssp_conv_s2_stats_tiles": [I, I, I, I, I, I],
+    "ssp_conv_s2_dgrad": [P, P, P, I, I, I, I, I, I, I, I, I, P],
+    "ssp_conv_s2_wgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
     "ssp_bn_act_bwd_partials": [P, I, P, I, P, I, P, P, P, P, I, I, I, I, F, I, P, I, I, P, P, P, P, P],
     "ssp_conv_wgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
     "ssp_conv_wgrad_route": [I, I, I, I, I, I, I, I],

@@ -20,6 +20,14 @@ int64_t ssp_wino_adj_ws_floats(int B, int H, int W, int Cout_dy, int Cin_dx, int
 int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                           int ldx, int R, hipStream_t stream);
 int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile);
+int ssp_conv_s2_tile_m(int B, int H, int W, int Cout, int R);
+int ssp_conv_s2_fwd_launch(const float* in, const float* wt, float* out, const float* bias, float* stats, int B, int H, int W,
+                           int Cin, int Cout, int ldin, int ldout, int R, int accumulate, const float* escale,
+                           float act_slope, hipStream_t stream);
+int ssp_conv_s2_dgrad_launch(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
+                             int lddy, int lddx, int R, int accumulate, hipStream_t stream);
+int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
+                             int ldx, int R, hipStream_t stream);
 int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                                int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream);
 int ssp_bn_fwd_finalize_launch(const float* stats, int ntile, int BM, int M, int C, const float* gamma,
@@ -305,6 +313,33 @@ int ssp_conv_dgrad_adj_bnbwd(const float* dy, const float* wt, float* dx, int B,
   return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, 0, workspace,
                                workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f, &f, true, dM);
 }
+// ---- stride-2 convolution (conv_strided.hip) ----
+int ssp_conv_s2_fwd(const float* in, const float* wt, float* out, const float* bias, float* stats, int B, int H, int W,
+                    int Cin, int Cout, int ldin, int ldout, int R, int accumulate, void* stream) {
+  return ssp_conv_s2_fwd_launch(in, wt, out, bias, stats, B, H, W, Cin, Cout, ldin, ldout, R, accumulate, nullptr, 1.f,
+                                (hipStream_t)stream);
+}
+int ssp_conv_s2_fwd_affine(const float* in, const float* wt, float* out, const float* scale, const float* shift, float slope,
+                           int B, int H, int W, int Cin, int Cout, int ldin, int ldout, int R, void* stream) {
+  return ssp_conv_s2_fwd_launch(in, wt, out, shift, nullptr, B, H, W, Cin, Cout, ldin, ldout, R, 0, scale, slope,
+                                (hipStream_t)stream);
+}
+int ssp_conv_s2_stats_tile_m(int B, int H, int W, int Cin, int Cout, int R) { return ssp_conv_s2_tile_m(B, H, W, Cout, R); }
+int ssp_conv_s2_stats_tiles(int B, int H, int W, int Cin, int Cout, int R) {
+  const int bm = ssp_conv_s2_tile_m(B, H, W, Cout, R);
+  if (bm == 0) return 0;
+  const int pad = R / 2;
+  return ssp_cdiv((int64_t)B * ((H + 2 * pad - R) / 2 + 1) * ((W + 2 * pad - R) / 2 + 1), bm);
+}
+int ssp_conv_s2_dgrad(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                      int lddx, int R, int accumulate, void* stream) {
+  return ssp_conv_s2_dgrad_launch(dy, wt, dx, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, accumulate, (hipStream_t)stream);
+}
+int ssp_conv_s2_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy, int ldx,
+                      int R, void* stream) {
+  return ssp_conv_s2_wgrad_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, (hipStream_t)stream);
+}
+
 int ssp_bn_act_bwd_partials(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
                             const float* shift, const float* mean, const float* invstd, int C, int B, int H, int W,
                             float slope, int training, float* partial, int npartial, int zero_after, float* dgamma,

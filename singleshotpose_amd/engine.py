@@ -361,8 +361,13 @@ class Plan(object):
             if t in ('convolutional', 'connected'):
                 if t == 'convolutional':
                     k, s = int(block['size']), int(block['stride'])
-                    if s != 1 or k not in (1, 3) or (k == 3 and not int(block['pad'])):
+                    if s not in (1, 2) or k not in (1, 3) or (k == 3 and not int(block['pad'])):
                         raise NotImplementedError("conv size=%d stride=%d pad=%s is outside the yolo-pose hot path" % (k, s, block['pad']))
+                    if s == 2 and prev is self.input_act:
+                        # the first block runs on the 4-channel kernel family of its own (csrc/conv_first.hip), stride 1 only
+                        raise NotImplementedError("block %d (convolutional): a stride-2 convolution on the network input "
+                                                  "(the first block's kernels are stride 1; csrc/conv_strided.hip serves "
+                                                  "every later position)" % ind)
                     bn = int(block['batch_normalize']) != 0
                     seq = net.models[ind]
                     conv, bnm = seq[0], (seq[1] if bn else None)
@@ -373,11 +378,11 @@ class Plan(object):
                     if prev.H != 1 or prev.W != 1:
                         raise NotImplementedError("connected block %d on a %d x %d map: nn.Linear needs a (B, C) input - put "
                                                   "an avgpool (or a 1x1 map) in front of it" % (ind, prev.H, prev.W))
-                    k, bn, bnm = 1, False, None
+                    k, s, bn, bnm = 1, 1, False, None
                     m = net.models[ind]
                     conv = m[0] if isinstance(m, torch.nn.Sequential) else m
                 cs = _ConvSpec()
-                cs.ind, cs.k = ind, k
+                cs.ind, cs.k, cs.stride = ind, k, s
                 cs.bn = bn
                 act = block['activation']
                 if act not in _SLOPES:
@@ -394,7 +399,13 @@ class Plan(object):
                 if prev.ld < cs.cinp:
                     raise NotImplementedError("block %d (%s): its %d-channel input map has a row stride of %d floats, narrower "
                                               "than the padded channel count %d" % (ind, t, cs.cin, prev.ld, cs.cinp))
-                cs.H, cs.W = prev.H, prev.W
+                # Hi x Wi: the map the block reads; H x W: the map its convolution writes (raw output, BatchNorm / activation /
+                # fused pool input, M pixels).  The two differ for a stride-2 block only (csrc/conv_strided.hip).
+                cs.Hi, cs.Wi = prev.H, prev.W
+                cs.H, cs.W = (h, w) if s == 2 else (prev.H, prev.W)
+                if s == 2 and (cs.H, cs.W) != ((cs.Hi + 2 * (k // 2) - k) // 2 + 1, (cs.Wi + 2 * (k // 2) - k) // 2 + 1):
+                    raise NotImplementedError("block %d (convolutional): layer_shapes gives a %d x %d output for a %d x %d "
+                                              "input at stride 2" % (ind, w, h, cs.Wi, cs.Hi))
                 cs.coutp = _pad4(c)
                 cs.conv, cs.bnm = conv, bnm
                 # fuse a following 2x2/2 max-pool when it is the only consumer
@@ -581,6 +592,13 @@ class Plan(object):
         counted format of a Winograd launch), their count, the launch's workspace need; the statistics buffer is sized
         for the largest format any timed family of the layer uses, so a plan change never re-allocates it."""
         B = self.B
+        if cs.stride == 2:       # no plan codes, no workspace: one tile format (ssp_conv_s2_stats_tile_m)
+            cs.tile_m = _lib.query('ssp_conv_s2_stats_tile_m', B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.k)
+            cs.ntile = _lib.query('ssp_conv_s2_stats_tiles', B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.k)
+            cs.ws_fwd = 0
+            if cs.bn and cs.stats is None:
+                cs.stats = torch.empty(cs.ntile * cs.cout * 2, dtype=torch.float32, device=self.device)
+            return
         q = lambda name, code: _lib.query(name, B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
         cs.tile_m = q('ssp_conv_stats_tile_m', cs.plan_fwd)
         cs.ws_fwd = q('ssp_conv_workspace_floats', cs.plan_fwd)
@@ -887,6 +905,8 @@ class Plan(object):
         elif self._tune:
             wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
             for cs in self.convs.values():
+                if cs.stride != 1:      # no plan codes (and its key would be a stride-1 layer's of the same shape)
+                    continue
                 key = self._dgrad_key(cs)
                 # (the code that was verified, not just the key: a cached Winograd code that SSP_WINOGRAD=0 kept out of
                 # this process must not come back through this fallback)
@@ -896,8 +916,8 @@ class Plan(object):
         if tune:
             self._sync_codes(1)              # multi-GPU: ... and rank 0's data- / filter-gradient choices
         for cs in self.convs.values():
-            cs.ws_dgrad = 0 if cs.first else _lib.query('ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp,
-                                                        cs.cin, cs.k, cs.plan_dgrad)
+            cs.ws_dgrad = 0 if (cs.first or cs.stride == 2) else _lib.query(
+                'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
         self._plan_bn_fusion()
         self._fit_workspace()
 
@@ -908,7 +928,7 @@ class Plan(object):
         layer's plan codes alone; applied where the layer's data-gradient operand is prepared (_repack_dgrad), so the
         operand and the launch that reads it always agree."""
         t = wino_tile(cs.plan_dgrad)
-        return bool(_SHARE_DM and not cs.first and t and not wino_fused(cs.plan_dgrad) and cs.wgrad_wino == t and
+        return bool(_SHARE_DM and not cs.first and cs.stride == 1 and t and not wino_fused(cs.plan_dgrad) and cs.wgrad_wino == t and
                     cs.coutp == cs.cout)
 
     def _wgrad_key(self, cs):
@@ -931,8 +951,8 @@ class Plan(object):
         for cs in self.convs.values():
             cs.wgrad_wino = 0
             cmin = min(cs.cin, cs.cout)
-            if not (wino_on and cs.k == 3 and not cs.first and cs.cinp == cs.cin and cs.coutp == cs.cout and
-                    cs.cin % 16 == 0 and cs.cout % 16 == 0):
+            if not (wino_on and cs.k == 3 and cs.stride == 1 and not cs.first and cs.cinp == cs.cin and
+                    cs.coutp == cs.cout and cs.cin % 16 == 0 and cs.cout % 16 == 0):
                 continue
             # tile sizes worth timing: F(2x2) from SSP_WINO_MIN_CHANNELS (128) channels on both sides, F(4x4) from 64 ...
             ts_ok = [t for t in tiles if cmin >= 64 and cmin >= int(os.environ.get('SSP_WINO_MIN_CHANNELS', '128') if t == 2 else
@@ -1048,7 +1068,7 @@ class Plan(object):
         if not on:
             return
         for cs in self.convs.values():
-            if cs.first:
+            if cs.first or cs.stride != 1:      # (the strided data gradient has no fused sums: its producer keeps two passes)
                 continue
             src = cs.inp.producer
             scs = self.convs.get(src)
@@ -1102,7 +1122,7 @@ class Plan(object):
         # ring depth 8 = the latency form of the kernel (one workgroup per CU, 7 chunks in flight): only worth timing on
         # grids that cannot give a CU several workgroups anyway (small-batch inference)
         lat = IGEMM_LATENCY_CANDS
-        elig = [cs for cs in self.convs.values() if cs.cinp % 16 == 0]
+        elig = [cs for cs in self.convs.values() if cs.cinp % 16 == 0 and cs.stride == 1]
         if not elig:
             return
         # Winograd F(2x2, 3x3) candidates (csrc/conv_wino.hip): 16/36 of the multiplies at the price of two HBM-bound
@@ -1571,6 +1591,11 @@ class Plan(object):
             # inference, un-pooled block: BatchNorm affine + leaky folded into the conv epilogue - one launch,
             # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps).  Also
             # a block with its BatchNorm in eval() that no backward will visit (a frozen trunk under model.train()).
+            if cs.stride == 2:
+                call('ssp_conv_s2_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
+                     v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.inp.ld,
+                     cs.out.ld, cs.k, st)
+                return
             call('ssp_conv_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
                  v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld,
                  cs.out.ld, cs.k, cs.plan_fwd, self.ws.data_ptr(), self.ws_floats, st)
@@ -1598,9 +1623,13 @@ class Plan(object):
             call('ssp_wino_input_transform_t', cs.inp.ptr, cs.inp.ld, wws.data_ptr(), B, cs.H, cs.W, cs.cinp,
                  cs.wgrad_wino, self.side_stream.cuda_stream)
             cs.v_live = True
-        call('ssp_conv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias,
-             cs.stats.data_ptr() if use_stats else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
-             cs.k, 0, cs.plan_fwd, ws_t.data_ptr(), ws_t.numel(), st)
+        if cs.stride == 2:
+            call('ssp_conv_s2_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias, cs.stats.data_ptr() if use_stats else None,
+                 B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw, cs.k, 0, st)
+        else:
+            call('ssp_conv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias,
+                 cs.stats.data_ptr() if use_stats else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
+                 cs.k, 0, cs.plan_fwd, ws_t.data_ptr(), ws_t.numel(), st)
         if bn_train:
             bn = cs.bnm
             call('ssp_bn_fwd_finalize', cs.stats.data_ptr(), cs.ntile, cs.tile_m, cs.M, cs.cout,
@@ -1750,6 +1779,13 @@ class Plan(object):
         call = _lib.call
         B = self.B
         gin = self._grad_buf(src, cs.inp)
+        if cs.stride == 2:
+            # parity-decomposed data gradient (csrc/conv_strided.hip): H x W of the INPUT map, no plan, no workspace, no
+            # fused BatchNorm-backward sums (_plan_bn_fusion never makes a strided block the consumer)
+            call('ssp_conv_s2_dgrad', dy_ptr, _ptr(self._dpack, cs.doff), gin.ptr, B, cs.Hi, cs.Wi, cs.coutp, cs.cin, dy_ld,
+                 gin.ld, cs.k, 1 if src in written else 0, st)
+            written.add(src)
+            return
         scs = cs.bn_fuse_src
         dwt = (self._wino_ud(cs, wino_tile(cs.plan_dgrad)).data_ptr() if wino_tile(cs.plan_dgrad)
                else _ptr(self._dpack, cs.doff))
@@ -2041,6 +2077,7 @@ class Plan(object):
             side.wait_stream(main)          # dY(l) (and the zeroed packed-gradient buffer) are ready
         if s.wgrad:
             gw = gview(cs.conv.weight, cs.packed)
+            wg_name = 'ssp_conv_s2_wgrad' if cs.stride == 2 else 'ssp_conv_wgrad'      # (both take the INPUT map's H x W)
             if cs.packed and cs.wgrad_wino:
                 wws = self._wino_ws(cs)
                 # (dy = NULL: dM is in its slot of wws already, see above)
@@ -2049,10 +2086,10 @@ class Plan(object):
                      wws.numel(), st2)
                 cs.v_live = False
             elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
-                call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld,
+                call(wg_name, dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.Hi, cs.Wi, cs.cinp, cs.cout, dy_ld,
                      cs.inp.ld, cs.k, st2)
             else:
-                call('ssp_conv_wgrad', dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.H, cs.W, cs.cinp,
+                call(wg_name, dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.Hi, cs.Wi, cs.cinp,
                      cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
                 call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
             out_grads[id(cs.conv.weight)] = gw
