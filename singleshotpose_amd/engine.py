@@ -1983,6 +1983,14 @@ class Plan(object):
             out_grads[id(prm)] = gv
             return gv
 
+        if cs.coutp != cs.cout:
+            # The padding columns of g are whatever its writers left: a strided data gradient writes cin of the cinp columns
+            # (the rest is torch.empty memory - NaN in a poisoned allocator), a stride-1 one the products of an unpacked
+            # operand's padding.  Every pass below reads coutp columns, and the in-place BatchNorm / activation backward
+            # writes them into the raw output, where the next forward's activation pass picks them up (the conv launch
+            # writes cout columns): 0 * NaN in this block's data gradient or in the consumer's forward.  Define them here.
+            with torch.cuda.stream(main):
+                g.t.view(-1, g.ld)[:, g.off + cs.cout:g.off + cs.coutp].zero_()
         if cs.first_live:
             # first block, fused form: every backward pass recomputes the convolution from the input.  The reductions
             # feed dy_raw, which each of the passes below needs (a frozen gamma / beta lands in scratch).

@@ -741,3 +741,21 @@ def choose_seeds(ok, n=24, pool=1000):
 
 GEN = [Seq('gen%03d' % s, random_sequence(s)) for s in GEN_SEEDS]
 ALL = HAND + GEN
+
+
+# ------------------------------------------------------------------------------------------------ a net with a strided block
+# topology case s2_bn_pair_producer-0: conv 8 -> 3x3 stride-2 BatchNorm conv 16 (ordinal 1 = mid) -> conv 16 -> head, shapes
+# 2 x 16 x 16 and 1 x 24 x 24.  The strided block's packed forward filter and its data-gradient operand sit behind the same
+# version keys as every other block's; the hand-written sequences write its filter in place, relayout it and freeze it
+# (kfreeze = 2), and three generated ones: the first seed whose sequence on this net writes the filter of ordinal 1 in place
+# (perturb_w / perturb_w_data), the first with a load_weights between two training steps (the data-gradient operand is
+# packed again from the loaded filter), and the first that writes that filter after a relayout(1) and then takes two
+# fused steps in front of an eval (a relayouted filter is not the forward operand: it is packed, behind the version key),
+# all passing the visibility and tameness conditions of tests/test_sequences_cpu.py
+STRIDED_NET = case_net(T.CASES['s2_bn_pair_producer-0'], 1, 2)
+STRIDED_GEN_SEEDS = (12, 8, 212)
+
+
+def strided_sequences():
+    return [s for s in hand_sequences(STRIDED_NET) if s.id in TUNED_HAND] + \
+        [Seq('gen%03d' % s, random_sequence(s, STRIDED_NET)) for s in STRIDED_GEN_SEEDS]

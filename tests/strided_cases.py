@@ -37,7 +37,40 @@ CASES = [
 DGRAD_UNSPLIT = Case((4, 128, 128, 4, 8, 3), None, 0)
 
 
+# Channel counts with C % 4 == 2, as an 18- or 6-filter block hands them to the plan.  Forward / filter gradient: Cout of
+# 18 and 6 into ldout = lddy = pad4(Cout).  Data gradient: Cin_dx of 18 and 6 (the plan passes the unpadded count) into
+# lddx = pad4(Cin_dx) and into a slice of a wider buffer; 3x3 on a small grid (taps split over workgroups, atomics), 3x3 on
+# the smallest grid that is not split (four classes of 128 tiles of 128 pixels: 4 x 128 x 128, as DGRAD_UNSPLIT), and 1x1
+# (the zero fill of the three parity classes without a tap).  Every column of the destination outside its C channels holds
+# SENTINEL before the launch and after it.
+SENTINEL = 77.0
+PAD_OUT = [Case((2, 7, 10, 8, 18, 3), None, 0), Case((2, 8, 5, 12, 6, 1), None, 0)]
+DgradPad = collections.namedtuple('DgradPad', 'shape lddx off')
+PAD_DGRAD = [
+    DgradPad((2, 7, 10, 18, 8, 3), 20, 0), DgradPad((2, 7, 10, 6, 12, 3), 8, 0),
+    DgradPad((3, 13, 13, 18, 24, 3), 32, 8), DgradPad((2, 8, 5, 6, 8, 3), 16, 4),
+    DgradPad((4, 128, 128, 18, 8, 3), 20, 0), DgradPad((4, 128, 128, 6, 8, 3), 12, 4),
+    DgradPad((2, 9, 12, 18, 8, 1), 20, 0), DgradPad((2, 8, 5, 6, 12, 1), 16, 8),
+]
+
+
+def dgrad_workgroups(shape):
+    """(workgroups of the unsplit data-gradient launch, whether it is split by taps): include/ssp_hip.h, ssp_conv_s2_dgrad -
+    3x3 launches of fewer than 512 workgroups are; tiles of 128 rows, 64 where those would leave CUs of the 256 idle, and
+    of 64 (Cin_dx <= 64) or 128 columns."""
+    B, H, W, Cin, Cout, R = shape
+    Ms = [B * ((H - py + 1) // 2) * ((W - px + 1) // 2) for py in (0, 1) for px in (0, 1) if R == 3 or not (py or px)]
+    Ms = [m for m in Ms if m > 0]
+    bn = 128 if Cin > 64 else 64
+    ncol = (Cin + bn - 1) // bn
+    bm = 64 if sum((m + 127) // 128 for m in Ms) * ncol < 256 else 128
+    wgs = sum((m + bm - 1) // bm for m in Ms) * ncol
+    return wgs, R == 3 and wgs < 512
+
+
 def case_id(c):
+    if isinstance(c, DgradPad):
+        return '%dx%dx%d-%dto%d-r%d-ld%d+%d' % (c.shape + (c.lddx, c.off))
     return '%dx%dx%d-%dto%d-r%d%s' % (c.shape + ('-ld%d' % c.ld if c.ld else '',))
 
 

@@ -231,6 +231,24 @@ def test_sequence(seq, monkeypatch, tmp_path):
     run_sequence(seq, S.TINY_NET, model, monkeypatch, tmp_path)
 
 
+# ---------------------------------------------------------------------------------------------------- a strided block
+STRIDED_SEQS = S.strided_sequences()
+
+
+@pytest.mark.parametrize('seq', STRIDED_SEQS, ids=ids(STRIDED_SEQS))
+def test_sequence_on_a_net_with_a_strided_block(seq, monkeypatch, tmp_path):
+    """S.STRIDED_NET: the packed forward filter and the data-gradient operand of a stride-2 BatchNorm block (conv ordinal 1)
+    across in-place writes, a relayout, frozen prefixes, optimizer steps in every layout, load_weights and graph replay."""
+    monkeypatch.setenv('SSP_AUTOTUNE', '0')
+    monkeypatch.delenv('SSP_TUNE_CACHE', raising=False)
+    net = S.STRIDED_NET
+    model = S.build_model(net).cuda()
+    run_sequence(seq, net, model, monkeypatch, tmp_path)
+    plan = model._plans[net.shapes['A'] + (torch.cuda.current_device(),)]
+    cs = plan.convs[sorted(plan.convs)[net.mid]]
+    assert cs.stride == 2 and cs.bn
+
+
 # ---------------------------------------------------------------------------------------------------- tuned plans
 TUNED_CASE = T.CASES[T.TUNED[0]]
 TUNED_NET = S.case_net(TUNED_CASE, 2, 2)       # conv ordinals 2 and 3 are the 64 -> 64 3x3 layers; the first two blocks freeze

@@ -28,7 +28,7 @@ def _data(c):
     """Operands and int64 references of a case, computed once and shared (never modified) by the tests below."""
     B, H, W, Cin, Cout, R = c.shape
     x, dy, w = S.operands(c.shape)
-    if c is S.DGRAD_UNSPLIT:
+    if c is S.DGRAD_UNSPLIT or isinstance(c, S.DgradPad):
         return dict(dy=dy, w=w, dgrad=S.ref_dgrad(dy, w, H, W))
     return dict(x=x, dy=dy, w=w, fwd=S.ref_fwd(x, w), dgrad=S.ref_dgrad(dy, w, H, W), wgrad=S.ref_wgrad(dy, x, R))
 
@@ -160,6 +160,88 @@ def test_filter_gradient_exact(c):
               G.stream())
     torch.cuda.synchronize()
     _assert_equal(dw.cpu(), d['wgrad'].float(), ('co', 'tap', 'ci'))
+
+
+# ------------------------------------------------------------------------------------------------ C % 4 == 2
+def _sentinel_kept(buf, lo, hi):
+    """Every column outside [lo, hi) still holds S.SENTINEL."""
+    b = buf.cpu()
+    rest = torch.cat([b[:, :lo], b[:, hi:]], 1)
+    return rest.numel() > 0 and bool((rest == S.SENTINEL).all())
+
+
+@pytest.mark.parametrize('c', S.PAD_OUT, ids=S.case_id)
+def test_forward_and_filter_gradient_with_padded_cout(c):
+    """Cout of 18 and 6 into ldout = lddy = pad4(Cout): the forward writes Cout columns and leaves the two behind them
+    alone (plain, and accumulating with a bias); the filter gradient reads dy rows of pad4(Cout) floats."""
+    G, _lib = _imports()
+    B, H, W, Cin, Cout, R = c.shape
+    Ho, Wo = S.out_hw(H, W, R)
+    d = _data(c)
+    ldx, ldy, off = S.buffers(c)
+    assert Cout % 4 == 2 and ldy == Cout + 2 and off == 0
+    M = B * Ho * Wo
+    xd = E.nhwc_buffer(d['x'], ldx).to(G.dev())
+    wd = E.pack_fwd(d['w']).float().to(G.dev())
+    want = d['fwd'].reshape(M, Cout).float()
+    cinp = E.pad4(Cin)
+    ntile = _lib.query('ssp_conv_s2_stats_tiles', B, H, W, cinp, Cout, R)
+    stats = torch.full((ntile * Cout * 2,), NAN, dtype=torch.float32, device=G.dev())
+    out = torch.full((M, ldy), S.SENTINEL, dtype=torch.float32, device=G.dev())
+    _lib.call('ssp_conv_s2_fwd', xd.data_ptr(), wd.data_ptr(), out.data_ptr(), None, stats.data_ptr(), B, H, W, cinp, Cout,
+              ldx, ldy, R, 0, G.stream())
+    torch.cuda.synchronize()
+    _assert_equal(out.cpu()[:, :Cout], want, ('pixel', 'co'))
+    assert _sentinel_kept(out, 0, Cout)
+    assert bool(torch.isfinite(stats).all())
+    pre = E.prefill(c.shape, (M, Cout))
+    bias = torch.arange(Cout, dtype=torch.float32) - 3
+    out2 = torch.full((M, ldy), S.SENTINEL, dtype=torch.float32)
+    out2[:, :Cout] = pre.float()
+    out2 = out2.to(G.dev())
+    bd = bias.to(G.dev())
+    _lib.call('ssp_conv_s2_fwd', xd.data_ptr(), wd.data_ptr(), out2.data_ptr(), bd.data_ptr(), None, B, H, W, cinp, Cout, ldx,
+              ldy, R, 1, G.stream())
+    torch.cuda.synchronize()
+    _assert_equal(out2.cpu()[:, :Cout], want + bias + pre.float(), ('pixel', 'co'))
+    assert _sentinel_kept(out2, 0, Cout)
+    # filter gradient: dy as the plan holds it, zero pad columns
+    dyd = E.nhwc_buffer(d['dy'], ldy).to(G.dev())
+    dw = torch.zeros(d['wgrad'].shape, dtype=torch.float32, device=G.dev())
+    _lib.call('ssp_conv_s2_wgrad', dyd.data_ptr(), xd.data_ptr(), dw.data_ptr(), B, H, W, cinp, Cout, ldy, ldx, R, G.stream())
+    torch.cuda.synchronize()
+    _assert_equal(dw.cpu(), d['wgrad'].float(), ('co', 'tap', 'ci'))
+    # ... and as the source of a data gradient: Cout_dy = the padded count
+    dx = torch.full((B * H * W, ldx), S.SENTINEL, dtype=torch.float32, device=G.dev())
+    wdg = E.pack_dgrad(d['w']).float().to(G.dev())
+    _lib.call('ssp_conv_s2_dgrad', dyd.data_ptr(), wdg.data_ptr(), dx.data_ptr(), B, H, W, ldy, Cin, ldy, ldx, R, 0, G.stream())
+    torch.cuda.synchronize()
+    _assert_equal(dx.cpu()[:, :Cin], d['dgrad'].reshape(-1, Cin).float(), ('pixel', 'ci'))
+
+
+@pytest.mark.parametrize('accumulate', [0, 1], ids=['plain', 'acc'])
+@pytest.mark.parametrize('c', S.PAD_DGRAD, ids=S.case_id)
+def test_data_gradient_with_padded_cin(c, accumulate):
+    """Cin_dx of 18 and 6 (the unpadded count, as the plan passes it) into lddx = pad4(Cin_dx) or a slice of a wider buffer:
+    the scatter epilogue, the zero fill in front of a tap-split or 1x1 launch and the atomic adds write Cin_dx columns;
+    every other column keeps its sentinel."""
+    G, _lib = _imports()
+    B, H, W, Cin, Cout, R = c.shape
+    d = _data(c)
+    assert Cin % 4 == 2 and c.off + E.pad4(Cin) <= c.lddx
+    dyd = E.nhwc_buffer(d['dy']).to(G.dev())
+    wd = E.pack_dgrad(d['w']).float().to(G.dev())
+    M = B * H * W
+    pre = E.prefill(c.shape, (M, Cin))
+    dx = torch.full((M, c.lddx), S.SENTINEL, dtype=torch.float32)
+    dx[:, c.off:c.off + Cin] = pre.float() if accumulate else NAN
+    dx = dx.to(G.dev())
+    _lib.call('ssp_conv_s2_dgrad', dyd.data_ptr(), wd.data_ptr(), G.p(dx, c.off), B, H, W, E.pad4(Cout), Cin, E.pad4(Cout),
+              c.lddx, R, accumulate, G.stream())
+    torch.cuda.synchronize()
+    want = d['dgrad'].reshape(M, Cin).float() + (pre.float() if accumulate else 0)
+    _assert_equal(dx.cpu()[:, c.off:c.off + Cin], want, ('pixel', 'ci'))
+    assert _sentinel_kept(dx, c.off, c.off + Cin)
 
 
 # ------------------------------------------------------------------------------------------------ argument checks

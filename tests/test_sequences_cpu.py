@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import sequence_cases as S
+import topology_cases as T
 from helpers import rel_err
 
 NET = S.TINY_NET
@@ -15,15 +16,15 @@ VISIBLE = 1e-2       # 100 x the project's forward bar of 1e-4
 ids = lambda seqs: [s.id for s in seqs]
 
 
-def _runs(seq, cache={}):
-    if seq.id not in cache:
-        cache[seq.id] = S.run_reference(NET, seq.ops)
-    return cache[seq.id]
+def _runs(seq, net=NET, cache={}):
+    if (net.name, seq.id) not in cache:
+        cache[net.name, seq.id] = S.run_reference(net, seq.ops)
+    return cache[net.name, seq.id]
 
 
-def visibility(ops):
+def visibility(ops, net=NET):
     """[(position, mutation kind, observer position, observer kind, rel_err of the observer's head with / without)]."""
-    seen, _ = S.run_reference(NET, ops)
+    seen, _ = S.run_reference(net, ops)
     with_ = {pos: got['y'] for pos, _, got in seen}
     out = []
     for i, o in enumerate(ops):
@@ -33,7 +34,7 @@ def visibility(ops):
         if j is None:
             out.append((i, o.kind, None, None, 0.0))
             continue
-        without, _ = S.run_reference(NET, ops, skip=i, stop=j + 1)
+        without, _ = S.run_reference(net, ops, skip=i, stop=j + 1)
         y0 = without[-1][2]['y']
         out.append((i, o.kind, j, ops[j].kind, rel_err(with_[j].numpy(), y0.numpy())))
     return out
@@ -73,6 +74,38 @@ def test_the_reference_stays_tame(seq):
     ok, worst = tame(seen)
     print('SEQ %s %d observations, max|y| / first of its mode: %.2f' % (seq.id, len(seen), worst))
     assert seen and ok, (seq.id, worst)
+
+
+STRIDED = S.strided_sequences()
+
+
+@pytest.mark.parametrize('seq', STRIDED, ids=ids(STRIDED))
+def test_the_strided_net_sees_every_mutation_and_stays_tame(seq):
+    """The same two conditions for the sequences tests/test_gpu_sequences.py runs on S.STRIDED_NET; and they do write the
+    strided block's filter, running statistics and frozen prefix."""
+    net = S.STRIDED_NET
+    info = T.layer_info(T.blocks_of(net.case), net.case.H, net.case.W)
+    convs = [l for l in info if l.type == 'convolutional']
+    assert net.case.channels == 3 and T._is_s2(convs[net.mid]) and T._is_bn(convs[net.mid]) and net.mid < net.kfreeze
+    rows = visibility(seq.ops, net)
+    for i, kind, j, okind, e in rows:
+        print('SEQ strided %s op %d %s -> op %s %s: %.3e' % (seq.id, i, kind, j, okind, e))
+        assert j is not None and e >= VISIBLE, (seq.id, i, kind, j, okind, e)
+    assert rows
+    seen, _ = _runs(seq, net)
+    ok, worst = tame(seen)
+    assert seen and ok, (seq.id, worst)
+
+
+def test_the_strided_sequences_reach_the_strided_block():
+    net = S.STRIDED_NET
+    assert len(STRIDED) == 6 and len(set(s.id for s in STRIDED)) == 6
+    ops = [o for s in STRIDED for o in s.ops]
+    for kind in ('perturb_w', 'perturb_w_data', 'relayout', 'perturb_running'):
+        assert any(o.kind == kind and o.args == (net.mid,) for o in ops), kind
+    assert any(o.kind == 'freeze_prefix' and o.args[0] > net.mid for o in ops)
+    for kind in ('load_weights', 'eval_graph', 'fused_step', 'group_step', 'torch_step', 'train_step'):
+        assert any(o.kind == kind for o in ops), kind
 
 
 def test_generated_sequences_keep_their_form():

@@ -11,7 +11,10 @@ import strided_cases as S
 ids = [S.case_id(c) for c in S.CASES]
 
 
-@pytest.mark.parametrize('c', S.CASES, ids=ids)
+ALL = S.CASES + S.PAD_OUT + S.PAD_DGRAD
+
+
+@pytest.mark.parametrize('c', ALL, ids=[S.case_id(c) for c in ALL])
 def test_references_equal_conv2d_and_its_autograd(c):
     B, H, W, Cin, Cout, R = c.shape
     x, dy, w = S.operands(c.shape)
@@ -44,7 +47,33 @@ def test_case_table_covers_what_it_says():
     assert any(s[4] % 32 for s in shapes)
 
 
-@pytest.mark.parametrize('c', S.CASES + [S.DGRAD_UNSPLIT], ids=ids + [S.case_id(S.DGRAD_UNSPLIT)])
+def test_padded_case_tables_cover_what_they_say():
+    """C % 4 == 2 on the side that is written; the data-gradient table holds tap-split, unsplit and 1x1 launches, each into
+    pad4(Cin_dx) columns and into a slice of a wider buffer, and the unsplit shapes are the smallest such."""
+    for c in S.PAD_OUT:
+        assert c.shape[4] % 4 == 2 and S.buffers(c)[1] == c.shape[4] + 2
+    assert sorted(c.shape[5] for c in S.PAD_OUT) == [1, 3]
+    kinds = set()
+    for c in S.PAD_DGRAD:
+        B, H, W, Cin, Cout, R = c.shape
+        assert Cin in (6, 18) and c.off % 4 == 0 and c.off + E.pad4(Cin) <= c.lddx
+        wgs, split = S.dgrad_workgroups(c.shape)
+        kinds.add((R, split, c.lddx == E.pad4(Cin), Cin))
+        if R == 3 and not split:
+            assert wgs == 512 and S.dgrad_workgroups((B, H - 1, W, Cin, Cout, R))[1]
+            assert B * H * W * c.lddx * 4 <= 8 << 20          # a few MB
+    for Cin in (6, 18):
+        assert set(k[:2] for k in kinds if k[3] == Cin) == {(3, True), (3, False), (1, False)}
+    assert set((k[0], k[1], k[2]) for k in kinds) >= {(3, True, True), (3, True, False), (3, False, True), (3, False, False),
+                                                      (1, False, True), (1, False, False)}
+    assert S.dgrad_workgroups(S.DGRAD_UNSPLIT.shape) == (512, False)
+    assert all(S.dgrad_workgroups(c.shape)[1] for c in S.CASES if c.shape[5] == 3)      # (as strided_cases says of them)
+
+
+PARITY = S.CASES + [S.DGRAD_UNSPLIT] + S.PAD_DGRAD
+
+
+@pytest.mark.parametrize('c', PARITY, ids=[S.case_id(c) for c in PARITY])
 def test_parity_decomposition_reproduces_the_data_gradient(c):
     """Four dense contractions over 1, 2, 2 and 4 taps (3x3) - or one over the single tap (1x1) - give the scatter
     reference on odd and even maps; no class walks a tap that cannot reach it."""

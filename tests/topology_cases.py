@@ -9,6 +9,8 @@ A case is a cfg body plus (B, H, W, channels) and a weight seed.  Three families
   exact  the same grammar without BatchNorm / leaky / softmax, on integer data: every activation, gradient and
          filter-gradient partial sum is an integer (or a multiple of 1 / avgpool pixels) below 2^24 grid steps
          (exact_budget), so fp32 in any summation order is exact and the product must be torch.equal to float64
+  gs2 / xs2  the gen and exact families with stride-2 convolutions in the grammar (random_case(seed, exact, strided=True)), on
+         maps that are also odd
 Float cases carry a data seed (SEEDS) under which every leaky / relu sign and every max-pool winner has a margin of at
 least 4x the float32-against-float64 forward difference of the CPU reference: a flipped decision moves a gradient by far
 more than rounding does, and the bars of the GPU test are rounding bars.
@@ -28,9 +30,9 @@ Case = collections.namedtuple('Case', 'id family body B H W channels wseed')
 
 
 # ------------------------------------------------------------------------------------------------ cfg text
-def conv(f, k=3, bn=1, act='leaky'):
-    return '[convolutional]\n%sfilters=%d\nsize=%d\nstride=1\npad=1\nactivation=%s\n\n' % (
-        'batch_normalize=1\n' if bn else '', f, k, act)
+def conv(f, k=3, bn=1, act='leaky', stride=1):
+    return '[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\npad=1\nactivation=%s\n\n' % (
+        'batch_normalize=1\n' if bn else '', f, k, stride, act)
 
 
 def pool(stride=2):
@@ -115,6 +117,10 @@ def layer_info(blocks, H, W):
         if t == 'convolutional':
             c = int(b['filters'])
             ld = _pad4(c)
+            if int(b['stride']) == 2:      # nn.Conv2d(stride=2, padding=k // 2 with pad=1): odd maps round up
+                k = int(b['size'])
+                p = k // 2 if int(b['pad']) else 0
+                h, w = (h + 2 * p - k) // 2 + 1, (w + 2 * p - k) // 2 + 1
         elif t == 'maxpool':
             if int(b['stride']) == 2:
                 h, w = h // 2, w // 2
@@ -153,6 +159,10 @@ def _is_bn(l):
     return l.type == 'convolutional' and int(l.block['batch_normalize']) != 0
 
 
+def _is_s2(l):
+    return l.type == 'convolutional' and int(l.block['stride']) == 2
+
+
 def _in_shape(info, ind, blocks, H, W):
     if ind == 0:
         return int(blocks[0].get('channels', 3)), H, W, _pad4(int(blocks[0].get('channels', 3)))
@@ -164,9 +174,10 @@ def supported(blocks, B, H, W):
     """[] when a plan must run this cfg, else [(class, block index), ...]: what the reference's semantics and the ABI
     (include/ssp_hip.h) rule out.  Classes: 'route3' a route of more than two layers (darknet.py:99-106 handles one or two),
     'route_first' a two-layer route whose first is not the previous layer (darknet.py:206), 'concat4' a concatenated map with
-    C % 4 != 0 (ssp_copy_channels), 'odd' a standalone 2x2/2 max-pool or a reorg of a map with odd H or W, 'last4' a network
-    output with C % 4 != 0, 'narrow' a conv or connected block whose input rows are narrower than its padded Cin, 'reorg4' a
-    reorg of a map with C % 4 != 0."""
+    C % 4 != 0 (ssp_copy_channels), 'odd' a standalone 2x2/2 max-pool or a reorg of a map with odd H or W (the network input's,
+    or one a stride-2 conv made odd: 26 -> 13), 'last4' a network output with C % 4 != 0, 'narrow' a conv or connected block
+    whose input rows are narrower than its padded Cin, 'reorg4' a reorg of a map with C % 4 != 0, 'first_s2' a stride-2 conv
+    as block 0 (the first block's kernel family is stride 1 only; ssp_conv_s2_* serve every later position)."""
     info = layer_info(blocks, H, W)
     bad = []
     for ind, l in enumerate(info):
@@ -186,8 +197,11 @@ def supported(blocks, B, H, W):
                 bad.append(('odd', ind))
             if c % 4:
                 bad.append(('reorg4', ind))
-        elif l.type in ('convolutional', 'connected') and ld < _pad4(c):
-            bad.append(('narrow', ind))
+        elif l.type in ('convolutional', 'connected'):
+            if ld < _pad4(c):
+                bad.append(('narrow', ind))
+            if ind == 0 and _is_s2(l):
+                bad.append(('first_s2', ind))
     last = max(i for i, l in enumerate(info) if l.type not in ('region', 'cost'))
     if info[last].C % 4:
         bad.append(('last4', last))
@@ -195,7 +209,8 @@ def supported(blocks, B, H, W):
 
 
 def expected_fused_pool(blocks, B, H, W):
-    """Pool layers a plan folds into the BatchNorm block in front of them: the block's only consumer, on an even map."""
+    """Pool layers a plan folds into the BatchNorm block in front of them: the block's only consumer, on an even map (the
+    map the block WRITES: a stride-2 block's output, l.H x l.W of layer_info)."""
     info = layer_info(blocks, H, W)
     cons = consumers_of(info)
     return set(i + 1 for i, l in enumerate(info[:-1])
@@ -205,11 +220,26 @@ def expected_fused_pool(blocks, B, H, W):
 
 def expected_bn_fuse(blocks, B, H, W):
     """{consumer: source}: un-pooled BatchNorm blocks with unpadded channels whose only consumer is the conv / connected
-    block right behind them (their BatchNorm-backward sums ride in that block's data-gradient launch)."""
+    block right behind them (their BatchNorm-backward sums ride in that block's data-gradient launch).  A stride-2 block is
+    never the consumer - its data gradient has no fused sums - but may be the source: the sums then run over its output map."""
     info = layer_info(blocks, H, W)
     cons = consumers_of(info)
     return {i + 1: i for i, l in enumerate(info[:-1])
-            if _is_bn(l) and l.C % 4 == 0 and info[i + 1].type in ('convolutional', 'connected') and cons[i] == [i + 1]}
+            if _is_bn(l) and l.C % 4 == 0 and info[i + 1].type in ('convolutional', 'connected') and cons[i] == [i + 1] and
+            not _is_s2(info[i + 1])}
+
+
+def _bn_pair_but_for_stride(info, cons, i):
+    """Layer i would be the source of a fused BatchNorm-backward pair if the block behind it were not a stride-2 conv."""
+    l = info[i]
+    return _is_bn(l) and l.C % 4 == 0 and i + 1 < len(info) and _is_s2(info[i + 1]) and cons[i] == [i + 1]
+
+
+def _alias_root(info, i):
+    """The layer whose buffer layer i is: one-layer routes followed back (-1 = the network input)."""
+    while i >= 0 and info[i].type == 'route' and len(info[i].srcs) == 1:
+        i = info[i].srcs[0]
+    return i
 
 
 def live_layers(info):
@@ -228,8 +258,12 @@ def live_layers(info):
 # the hand-written cases' properties: each names a line of Plan that the shipped cfgs never reach
 HAND_PROPS = ('alias_pool_2cons', 'concat_src_shortcut_src', 'shortcut_m1_alias', 'dead_branch', 'reorg_alias_pool',
               'bn_pad_to_conv', 'bn_fuse_pair', 'channels1', 'softmax_map_conv', 'pool_after_relu_nobn', 'concat_same',
-              'pool_not_fused_2cons')
-GRAMMAR = ('conv1', 'conv3', 'bn', 'bias', 'leaky', 'linear', 'relu', 'maxpool2', 'maxpool_s1', 'reorg', 'route1_rel',
+              'pool_not_fused_2cons',
+              # ... and that no net with a stride-2 block reached before this table had one
+              's2_after_pad', 's2_reads_concat', 's2_alias_two_s2_consumers', 's2_bn_pair_producer', 's2_bn_pair_not_consumer',
+              's2_fused_pool', 's2_chain_odd', 's2_reorg_pool_s1', 's2_dead_and_head', 's2_classifier')
+S2_GRAMMAR = ('conv3_s2', 'conv1_s2', 's2_bn', 's2_bias', 's2_odd_in', 's2_head', 's2_fused_pool')
+GRAMMAR = S2_GRAMMAR + ('conv1', 'conv3', 'bn', 'bias', 'leaky', 'linear', 'relu', 'maxpool2', 'maxpool_s1', 'reorg', 'route1_rel',
            'route1_abs', 'route2', 'shortcut', 'shortcut_m1', 'shortcut_leaky', 'shortcut_linear', 'shortcut_relu', 'head',
            'classifier', 'connected2', 'softmax', 'B1', 'B2', 'B3', 'W16', 'Wnot16', 'first32_fused', 'first32_unfused',
            'channels1', 'channels3', 'pad_before_conv', 'fused_pool')
@@ -264,6 +298,38 @@ def features(blocks, B, H, W):
             if (_is_bn(l) and nxt is not None and nxt.type == 'maxpool' and nxt.block['stride'] == '2' and
                     l.H % 2 == 0 and l.W % 2 == 0 and len(cons[ind]) >= 2):
                 f.add('pool_not_fused_2cons')
+            if _is_s2(l):
+                _, hi, wi, _ = _in_shape(info, ind, blocks, H, W)
+                prev = info[ind - 1] if ind > 0 else None
+                f.add('conv%s_s2' % b['size'])
+                f.add('s2_bn' if _is_bn(l) else 's2_bias')
+                if hi % 2 or wi % 2:
+                    f.add('s2_odd_in')
+                if ind == len(info) - 1:
+                    f.add('s2_head')
+                if ind + 1 in fused:
+                    f.add('s2_fused_pool')
+                if prev is not None and prev.C % 4:
+                    f.add('s2_after_pad')
+                if prev is not None and prev.type == 'route' and len(prev.srcs) == 2:
+                    f.add('s2_reads_concat')
+                root = _alias_root(info, ind - 1)
+                if root != ind - 1 and any(k != ind and _is_s2(o) and _alias_root(info, k - 1) == root
+                                           for k, o in enumerate(info)):
+                    f.add('s2_alias_two_s2_consumers')
+                if ind > 0 and _bn_pair_but_for_stride(info, cons, ind - 1):
+                    f.add('s2_bn_pair_not_consumer')
+                if ind >= 3 and _is_s2(info[ind - 1]) and _is_s2(info[ind - 2]) and any(
+                        o.H % 2 or o.W % 2 for o in info[ind - 3:ind]):      # three in a row, an odd map among those they read
+                    f.add('s2_chain_odd')
+                if nxt is not None and (nxt.type == 'reorg' or (nxt.type == 'maxpool' and nxt.block['stride'] == '1' and
+                                                                  prev is not None and prev.type == 'maxpool' and
+                                                                  prev.block['stride'] == '1')):
+                    f.add('s2_reorg_pool_s1')
+                if ind not in live or ind == len(info) - 1:
+                    f.add('s2_dead_and_head')
+                if nxt is not None and nxt.type == 'avgpool':
+                    f.add('s2_classifier')
         elif t == 'maxpool':
             f.add('maxpool2' if b['stride'] == '2' else 'maxpool_s1')
         elif t == 'reorg':
@@ -302,8 +368,11 @@ def features(blocks, B, H, W):
                 f.add('softmax_map_conv')
     if fused:
         f.add('fused_pool')
-    if expected_bn_fuse(blocks, B, H, W):
+    pairs = expected_bn_fuse(blocks, B, H, W)
+    if pairs:
         f.add('bn_fuse_pair')
+    if any(_is_s2(info[s]) for s in pairs.values()):
+        f.add('s2_bn_pair_producer')
     return f
 
 
@@ -341,7 +410,19 @@ def ref_run(model, x, training, dtype=torch.float64, taps=None, absnet=False):
                     _tap(taps, 'pre', ind, x)
                     if absnet:
                         continue
-                x = m(x)
+                if isinstance(m, torch.nn.Conv2d):
+                    # stride and padding from the cfg (darknet.py:150-153: pad = (size - 1) // 2 if pad else 0), not from the
+                    # module the product built: a stride it dropped would otherwise be on both sides
+                    k = int(b['size'])
+                    assert tuple(m.weight.shape[2:]) == (k, k), (ind, tuple(m.weight.shape))
+                    s, p = int(b['stride']), (k - 1) // 2 if int(b['pad']) else 0
+                    if k == 1 and s > 1:
+                        # the same convolution on the pixels it reads (torch's float32 CPU backward of a strided 1x1
+                        # convolution corrupted the heap on some of these shapes)
+                        x, s = x[:, :, ::s, ::s], 1
+                    x = F.conv2d(x, m.weight, m.bias, stride=s, padding=p)
+                else:
+                    x = m(x)
         elif t == 'maxpool':
             _tap(taps, 'pool', ind, x)
             s = int(b['stride'])
@@ -567,16 +648,20 @@ _FILTERS = (6, 8, 12, 16, 18, 20, 24, 32, 64)
 _EXACT_FILTERS = (6, 8, 12, 16, 20)
 
 
-def random_case(seed, exact=False):
+def random_case(seed, exact=False, strided=False):
     """One case from the block grammar: conv 1x1 / 3x3 (stride 1, pad 1, BatchNorm or bias, leaky | linear | relu), max-pool
     2/2 and stride 1, reorg 2, a route of one layer (relative or absolute) or of two whose first is -1, a shortcut from any
     earlier layer of the same shape (-1 included), softmax on a map; then a linear conv head with 4k channels, or
     avgpool -> connected -> [connected] -> softmax.  4..9 blocks, B in {1, 2, 3}, 16..32 px, 1 or 3 input channels, 6..64
     filters, BatchNorm only where B * H * W >= 32.  exact: no BatchNorm, linear | relu, no softmax, avgpool only over a
-    power-of-two pixel count."""
-    rs = np.random.RandomState([seed, 7 if exact else 3])
+    power-of-two pixel count.
+    strided (the gs2 / xs2 families, a random stream of their own): a conv behind block 0 has stride 2 with probability 0.25
+    while its output stays at least 2 x 2; H and W are also drawn from 13, 15, 21, 26, so odd maps occur (a stride-2 conv
+    writes ceil(H / 2) x ceil(W / 2)); BatchNorm only where the map the block WRITES has B * Ho * Wo >= 32."""
+    rs = np.random.RandomState([seed, (11 if exact else 13) if strided else (7 if exact else 3)])
     B = int(rs.choice([1, 2, 3]))
-    H, W = int(rs.choice([16, 20, 24, 32])), int(rs.choice([16, 20, 24, 28, 32]))
+    odd = [13, 15, 21, 26] if strided else []
+    H, W = int(rs.choice([16, 20, 24, 32] + odd)), int(rs.choice([16, 20, 24, 28, 32] + odd))
     ch = int(rs.choice([1, 3]))
     n = int(rs.randint(4, 8 if exact else 10))
     classifier = rs.rand() < 0.3
@@ -593,7 +678,7 @@ def random_case(seed, exact=False):
     def spell(l):      # a layer index as the cfg writes it: relative, or absolute where the syntax can say it (> 0)
         return l if (l > 0 and rs.rand() < 0.5) else l - len(shapes)
 
-    if not exact and rs.rand() < 0.35 and B * H * W >= 32:
+    if not exact and rs.rand() < 0.35 and B * H * W >= 32 and H % 2 == 0 and W % 2 == 0:
         cur = add(conv(32, 3, 1, 'leaky'), (32, H, W))      # the fused first block (W % 16 == 0) and its fallback
         cur = add(pool(2), (32, H // 2, W // 2))
     ntail = (3 + int(rs.rand() < 0.5)) if classifier else 1
@@ -609,8 +694,11 @@ def random_case(seed, exact=False):
         ind = len(shapes)
         if kind == 'conv':
             f = int(rs.choice(filters))
+            s = 1
+            if strided and ind > 0 and h > 2 and w > 2 and rs.rand() < 0.25:
+                s, h, w = 2, (h + 1) // 2, (w + 1) // 2      # 1x1 pad 0 and 3x3 pad 1 alike
             bn = int(not exact and B * h * w >= 32 and rs.rand() < 0.6)
-            cur = add(conv(f, int(rs.choice([1, 3])), bn, str(rs.choice(acts))), (f, h, w))
+            cur = add(conv(f, int(rs.choice([1, 3])), bn, str(rs.choice(acts)), s), (f, h, w))
         elif kind == 'pool2' and h % 2 == 0 and w % 2 == 0 and h >= 4 and w >= 4:
             cur = add(pool(2), (c, h // 2, w // 2))
         elif kind == 'pool1' and ind > 0:
@@ -643,12 +731,13 @@ def random_case(seed, exact=False):
             body.append(softmax())
     else:
         body.append(head(int(rs.choice([4, 8, 12, 20]))))
-    return Case('%s%03d' % ('exact' if exact else 'gen', seed), 'exact' if exact else 'gen', ''.join(body), B, H, W, ch,
-                100 + seed)
+    name = ('xs2' if exact else 'gs2') if strided else ('exact' if exact else 'gen')
+    return Case('%s%03d' % (name, seed), 'exact' if exact else 'gen', ''.join(body), B, H, W, ch,
+                (300 if strided else 100) + seed)
 
 
-def random_cfg(seed, exact=False):
-    return cfg_text(random_case(seed, exact))
+def random_cfg(seed, exact=False, strided=False):
+    return cfg_text(random_case(seed, exact, strided))
 
 
 # ------------------------------------------------------------------------------------------------ the table
@@ -696,6 +785,51 @@ def _hand():
         # a BatchNorm block in front of a 2x2/2 pool whose un-pooled map a route reads as well: the pool must stay standalone
         add('pool_not_fused_2cons', i, c(8, 3, i != 1) + c(16, 3, 1, sact[i]) + pool() + c(16, 1 + 2 * (i % 2), 1) + route(1) +
             pool() + route(-1, 3) + head(8), B, H, W)
+    # ---- stride-2 blocks (ssp_conv_s2_*) meeting the rest of the plan.  Odd maps wherever the body allows them: a strided
+    # block writes ceil(H / 2) x ceil(W / 2), and its data gradient walks four parity classes of unequal size
+    odd = [(2, 16, 16), (1, 26, 22), (3, 13, 15)]
+    s2 = lambda f, k=3, bn=1, act='leaky': c(f, k, bn, act, 2)
+    for i, (B, H, W) in enumerate(odd):
+        # 18 (or 6) filters in front: Cin_dx % 4 == 2 of the data gradient, into a 20- (8-) wide gradient buffer whose padding
+        # columns nothing may write; forward and filter gradient read the padded map
+        add('s2_after_pad', i, c(6 if i == 2 else 18, 3, i != 1, sact[(i + 1) % 3]) + s2(16, 1 if i == 1 else 3) + head(8), B, H, W)
+        # the data gradient lands in a concat's gradient buffer and is split back to the two producers
+        add('s2_reads_concat', i, c(8) + c(8, 1 + 2 * (i % 2)) + route(-1, -2) + s2(16, 3 - 2 * (i % 2), i != 2, 'relu') + head(8),
+            B, H, W)
+        # one map read through aliases by a 3x3 and by a 1x1 strided block: the data gradient that runs second accumulates.
+        # The 1x1 form zeroes the three parity classes it has no tap for when it runs first (i = 0, 2: it is the later layer)
+        # and must leave them alone when it runs second (i = 1: the mirrored body)
+        ka, kb = (1, 3) if i == 1 else (3, 1)
+        add('s2_alias_two_s2_consumers', i, c(16) + route(-1) + s2(16, ka) + route(1) + s2(16, kb, i != 2) +
+            shortcut(-3, sact[i]) + head(8), B, H, W)
+        # a strided block as the SOURCE of a fused BatchNorm-backward pair: the sums run over its (smaller, odd) output map
+        add('s2_bn_pair_producer', i, c(8) + s2(16, 3 - 2 * (i % 2)) + c(16, 3, 1, sact[i]) + head(8), B, H, W)
+        # ... and never its consumer: layer 1 keeps the two-pass BatchNorm backward
+        add('s2_bn_pair_not_consumer', i, c(8) + c(16, 1 + 2 * (i % 2)) + s2(16, 3 - 2 * (i % 2), i != 1) + head(8), B, H, W)
+    for i, (B, H, W) in enumerate(sizes):
+        # a 2x2/2 pool folded into a strided BatchNorm block: the block's OUTPUT map is even
+        add('s2_fused_pool', i, c(8) + s2(16, 3 - 2 * (i % 2), 1, sact[(i + 1) % 3]) + pool() + head(8), B, H, W)
+    for i, (B, H, W) in enumerate([(2, 21, 15), (1, 26, 22), (3, 13, 15)]):
+        # three in a row, 26 x 22 -> 13 x 11 -> 7 x 6 -> 4 x 3: BatchNorm while the map a block writes has 32 pixels
+        add('s2_chain_odd', i, c(8) + s2(8, 3) + s2(12, 1) + s2(16, 3, 0, 'linear') + head(8), B, H, W)
+    for i, (B, H, W) in enumerate(sizes):
+        add('s2_reorg_pool_s1', i, c(8) + s2(8, 3, i == 1, 'relu') + reorg() + c(16, 1 + 2 * (i % 2)) + head(8), B, H, W)
+    for i, (B, H, W) in enumerate(odd):
+        add('s2_reorg_pool_s1', 3 + i, c(8) + pool(1) + s2(16, 3 - 2 * (i % 2), 1, sact[i]) + pool(1) + head(8), B, H, W)
+    for i, (B, H, W) in enumerate(odd):
+        # a strided block nothing downstream reads; a strided block as the network output (its dy is the caller's gradient)
+        add('s2_dead_and_head', i, c(8) + s2(8, 3 - 2 * (i % 2), i != 2) + route(-2) + head(8), B, H, W)
+        add('s2_dead_and_head', 3 + i, c(8, 3, 1, sact[i]) + s2(8, 1 + 2 * (i % 2), 0, 'linear'), B, H, W)
+        # avgpool over a strided map (56 and 143 pixels: no power of two)
+        add('s2_classifier', i, c(8) + s2(16, 3 - 2 * (i % 2)) + avgpool() + connected(8) + softmax(), B, H, W)
+    # a stride-1 and a stride-2 64 -> 64 3x3 layer on the same 64 x 8 x 8 map (layers 6 and 3), and a stride-1 64 -> 64 3x3 layer on
+    # the strided block's 4 x 4 output (layer 4): layers 3 and 4 launch data gradients of one shape key.  (Layers 4 and 6 are
+    # linear: 8192 more leaky signs leave no data seed in 0..7 with every margin)
+    add('wide', 4, c(16) + pool() + c(64) + s2(64) + c(64, 3, 1, 'linear') + route(2) + c(64, 3, 1, 'linear') + pool() +
+        route(-1, -4) + c(64, 3, 1, 'relu') + head(20), 2, 16, 16)
+    # ... behind a block without BatchNorm or activation: that block's own data gradient reads the gradient buffer as it is,
+    # padding columns included
+    add('s2_after_pad', 3, c(18, 3, 0, 'linear') + s2(16) + head(8), 1, 26, 22)
     return out
 
 
@@ -718,7 +852,20 @@ def _refused():
     add('last4-b', c(8) + avgpool() + connected(10) + softmax(), 2)
     add('narrow-a', c(18) + c(5) + route(-1, -2) + c(8) + head(8))     # a 23-channel concat in front of a conv
     add('narrow-b', c(6) + c(5, 1) + route(-1, -2) + head(8), 2)
+    add('first_s2-a', c(8, 3, 1, 'leaky', 2) + head(8))
+    add('first_s2-b', c(8, 1, 0, 'linear', 2) + c(8) + head(8), 2, 16, 24)
+    add('odd-s2-pool', c(8) + c(8, 3, 1, 'leaky', 2) + pool() + head(8), 1, 26, 22)       # 13 x 11 behind the strided block
+    add('odd-s2-reorg', c(8) + c(8, 1, 0, 'relu', 2) + reorg() + head(8), 1, 26, 22)
     return out
+
+
+def rank_one_first_block(case):
+    """A 1x1 BatchNorm conv on a one-channel input: every channel of its normalised output is + or - ONE map.  Its dbeta is
+    exactly zero and its dgamma a residue (gs2023: 5e-2 against 6e2 of summed |terms|, eps32 * 1.2e4 = 7e-4 of itself), so
+    the float32 CPU reference's own distance to float64 there - the bar of the GPU test - is one draw of rounding noise (1.8e-4
+    with torch's pairwise sums), not a measure of what fp32 can do.  The strided families leave such seeds out."""
+    b = blocks_of(case)[1]
+    return (case.channels == 1 and b['type'] == 'convolutional' and int(b['size']) == 1 and int(b['batch_normalize']) != 0)
 
 
 HAND = _hand()
@@ -731,14 +878,25 @@ GEN_SEEDS = (0, 1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 18, 19, 20, 21, 22, 
 EXACT_SEEDS = (0, 1, 2, 3, 4, 5, 9, 10, 11, 12, 13, 14, 28, 41, 52, 63)
 GEN = [random_case(s) for s in GEN_SEEDS]
 EXACT = [random_case(s, True) for s in EXACT_SEEDS]
-FLOAT = HAND + GEN
-CASES = {c.id: c for c in HAND + GEN + EXACT + REFUSED}
+# the strided families, chosen the same way: the first seeds of random_case(s, exact, strided=True) that `supported` passes,
+# that hold at least one stride-2 block, and that have a margin seed in 0..7 (gs2) or stay within the budget with a third of
+# the output and a tenth of dL/dx non-zero (xs2).  One more condition on gs2, from the reference alone (rank_one_first_block):
+# seeds 23 and 42 are passed over
+GS2_SEEDS = (0, 5, 7, 14, 15, 18, 20, 28, 29, 30, 37, 43)
+XS2_SEEDS = (0, 1, 2, 4, 6, 8, 12, 16, 18)
+GS2 = [random_case(s, False, True) for s in GS2_SEEDS]
+XS2 = [random_case(s, True, True) for s in XS2_SEEDS]
+# (the hand cases with a strided block go behind the earlier families: tests that take "the first n of FLOAT with ..." -
+# tests/test_finetune_cpu.py, tests/test_gpu_finetune.py - keep the cases they had)
+HAND_S2 = [c for c in HAND if c.id.startswith('s2_') or c.id == 'wide-4']
+FLOAT = [c for c in HAND if c not in HAND_S2] + GEN + HAND_S2 + GS2
+CASES = {c.id: c for c in HAND + GEN + GS2 + EXACT + XS2 + REFUSED}
 
 # cases the GPU test runs by more than one route (input-only backward, graph replay, a second step, both BatchNorm-backward
 # forms, a second batch size and resolution) and with tuned plans
 ROUTES = ('alias_pool_2cons-0', 'concat_src_shortcut_src-0', 'reorg_alias_pool-0', 'softmax_map_conv-0', 'channels1-0',
-          'gen012', 'concat_same-0', 'bn_pad_to_conv-0')
-TUNED = ('wide-0', 'wide-1', 'wide-2', 'wide-3')
+          'gen012', 'concat_same-0', 'bn_pad_to_conv-0', 's2_alias_two_s2_consumers-0', 'gs2020')
+TUNED = ('wide-0', 'wide-1', 'wide-2', 'wide-3', 'wide-4')
 VARIANTS = ('step2', 'b1', 'res2')
 
 
@@ -847,7 +1005,64 @@ SEEDS = {
  'wide-0': 4,
  'wide-1': 2,
  'wide-2': 4,
- 'wide-3': 0
+ 'wide-3': 0,
+ # the cases with stride-2 blocks
+ 's2_after_pad-0': 0,
+ 's2_reads_concat-0': 0,
+ 's2_alias_two_s2_consumers-0': 0,
+ 's2_bn_pair_producer-0': 0,
+ 's2_bn_pair_not_consumer-0': 1,
+ 's2_after_pad-1': 0,
+ 's2_reads_concat-1': 0,
+ 's2_alias_two_s2_consumers-1': 0,
+ 's2_bn_pair_producer-1': 0,
+ 's2_bn_pair_not_consumer-1': 0,
+ 's2_after_pad-2': 0,
+ 's2_after_pad-3': 0,
+ 's2_reads_concat-2': 0,
+ 's2_alias_two_s2_consumers-2': 0,
+ 's2_bn_pair_producer-2': 0,
+ 's2_bn_pair_not_consumer-2': 3,
+ 's2_fused_pool-0': 1,
+ 's2_fused_pool-1': 0,
+ 's2_fused_pool-2': 0,
+ 's2_chain_odd-0': 0,
+ 's2_chain_odd-1': 0,
+ 's2_chain_odd-2': 0,
+ 's2_reorg_pool_s1-0': 0,
+ 's2_reorg_pool_s1-1': 0,
+ 's2_reorg_pool_s1-2': 1,
+ 's2_reorg_pool_s1-3': 0,
+ 's2_reorg_pool_s1-4': 1,
+ 's2_reorg_pool_s1-5': 0,
+ 's2_dead_and_head-0': 0,
+ 's2_dead_and_head-3': 0,
+ 's2_classifier-0': 0,
+ 's2_dead_and_head-1': 0,
+ 's2_dead_and_head-4': 0,
+ 's2_classifier-1': 0,
+ 's2_dead_and_head-2': 0,
+ 's2_dead_and_head-5': 0,
+ 's2_classifier-2': 0,
+ 'wide-4': 0,
+ 'gs2000': 1,
+ 'gs2005': 0,
+ 'gs2007': 1,
+ 'gs2014': 0,
+ 'gs2015': 0,
+ 'gs2018': 2,
+ 'gs2020': 0,
+ 'gs2028': 0,
+ 'gs2029': 0,
+ 'gs2030': 1,
+ 'gs2037': 0,
+ 'gs2043': 5,
+ 'gs2020@b1': 1,
+ 'gs2020@res2': 1,
+ 'gs2020@step2': 0,
+ 's2_alias_two_s2_consumers-0@b1': 0,
+ 's2_alias_two_s2_consumers-0@res2': 0,
+ 's2_alias_two_s2_consumers-0@step2': 0
 }
 
 

@@ -1,6 +1,7 @@
-"""Writes tests/golden/generic_{pose,cls}.npz: the reference Darknet (imported read-only, as oracle/gen_golden.py does) run
-on the two cfgs that exercise the blocks outside the yolo-pose path - shortcut, stride-1 max-pool, non-BN relu / leaky
-convolutions (generic-pose.cfg); avgpool, connected, softmax, cost (generic-cls.cfg).
+"""Writes tests/golden/generic_{pose,cls,strided}.npz: the reference Darknet (imported read-only, as oracle/gen_golden.py
+does) run on the cfgs that exercise the blocks outside the yolo-pose path - shortcut, stride-1 max-pool, non-BN relu / leaky
+convolutions (generic-pose.cfg); avgpool, connected, softmax, cost (generic-cls.cfg); stride-2 convolutions, 3x3 and 1x1, on
+even and odd maps (generic-strided.cfg).
 
 Build machine only (the reference is not on the GPU machines); only the data it writes is committed.  Each file holds:
   weights           the seeded .weights byte stream (uint8), loaded by both sides
@@ -34,6 +35,7 @@ sys.path.insert(0, ROOT)
 CASES = (        # tag, cfg, B, H, W, weight seed, input seed
     ('pose', 'generic-pose.cfg', 2, 80, 80, 31, 131),
     ('cls', 'generic-cls.cfg', 4, 64, 64, 32, 132),
+    ('strided', 'generic-strided.cfg', 2, 40, 44, 33, 133),
 )
 NSLICE = 512
 
