@@ -58,6 +58,15 @@ int ssp_set_option(const char* name, int value);
  *   (ssp_conv_stats_tiles); accumulate, bias / affine and the fused BatchNorm-backward sums as for the other plans
  *   (bias / affine may be combined with accumulate, the BatchNorm-backward sums with neither).
  *   Valid for ssp_conv_fwd, ssp_conv_fwd_affine, ssp_conv_dgrad and ssp_conv_dgrad_bnbwd.
+ *   6000000 + tile_rows*100 + ksplit*10 + 3 (tile_rows 64|128, ksplit 1..9 with >= 8 K-steps of 16 per split) = the
+ *   bf16x3 fast mode of the direct kernel (conv_igemm_bf16x3.hip): same operands (`wt` from ssp_repack_fwd /
+ *   ssp_repack_dgrad, fp32), same workspace, statistics format and epilogue as the direct plan of that tile and split, but
+ *   every operand element is split on the chip into three bf16 terms (round to nearest even) and six of the nine term
+ *   products run on the bf16 matrix cores; the three dropped ones are at most 2^-24.3 of a product.  Needs Cin % 16 == 0,
+ *   Cout > 32 and % 4 == 0; a 6xxxxxx code on a launch it does not fit (ssp_conv_bf16x3_fits) is an error, never a run of
+ *   the fp32 kernel.  Non-finite inputs: an Inf operand (or a finite one within half a bf16 ulp of FLT_MAX) gives NaN
+ *   where the fp32 kernel gives Inf (Inf - Inf in the split).  Same four entry points; ssp_conv_plan_wino_tile returns
+ *   0 and the adjoint entry points refuse the code.
  * stats of a Winograd plan are in the COUNTED format: ssp_conv_stats_tile_m returns 0, the buffer holds
  *   [ssp_conv_stats_tiles(...)][Cout][2] (mean, M2) pairs followed by [ssp_conv_stats_tiles(...)] pixel counts
  *   (ssp_conv_stats_floats floats in all) and ssp_bn_fwd_finalize takes tile_m = 0. */
@@ -89,6 +98,10 @@ int64_t ssp_conv_wino_tiles(int B, int H, int W, int tile);
 int ssp_wino_filter_transform_t(const float* w9, float* U, int rows, int K, int tile, void* stream);
 int ssp_wino_filter_transform(const float* w9, float* U, int rows, int K, void* stream);
 int64_t ssp_conv_workspace_floats(int B, int H, int W, int Cin, int Cout, int R, int plan);
+/* 1 when a launch of that shape runs under the bf16x3 code `plan` (6xxxxxx, above), 0 when the entry points would
+ * refuse it (bad code, Cin % 16, Cout <= 32 or % 4, R not 1 | 3, a split with fewer than 8 K-steps, 2^31 pixels or
+ * more).  A pure host function: no GPU is touched.  Operand alignment and the workspace are checked by the launch. */
+int ssp_conv_bf16x3_fits(int B, int H, int W, int Cin, int Cout, int R, int plan);
 
 /* data gradient (autograd of nn.Conv2d, train.py:103): dx[p][ci] (+)= sum dy[p - tap][co] * w[co][ci][tap];
  * same contraction as ssp_conv_fwd with `wt` from ssp_repack_dgrad; Cout_dy = channels of dy (multiple of 4). */

@@ -112,6 +112,7 @@ _SIGS = {
     "ssp_prof_enable": [I],
     "ssp_prof_nkinds": [],
     "ssp_prof_collect": [P, P, P],
+    "ssp_conv_bf16x3_fits": [I, I, I, I, I, I, I],
 }
 
 _RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_dgrad_adj_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',

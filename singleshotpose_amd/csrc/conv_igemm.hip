@@ -20,6 +20,7 @@
 // ds_read_b128/b64 and feeds them to VEC successive MFMAs.
 #include "conv_igemm_common.h"
 #include "conv_wino.h"
+#include "conv_bf16x3.h"
 
 // ABL: 0 = product kernel; ablation bits for tools/conv_bench.py only (results are garbage): 1 no global loads in
 // the K loop, 2 no MFMA, 4 no barrier, 8 no fragment reads, 16 no LDS stores
@@ -436,6 +437,12 @@ struct IgemmPlan { int bm, ksplit, slots, tail; };   // slots: LDS ring depth of
                                                       // tail: K split of the last partial wave's tiles (hybrid launch), 0 = off
 static IgemmPlan select_plan(int M, int Cin, int Cout, int R, int plan_code) {
   IgemmPlan pl = {256, 1, 0, 0};
+  if (ssp_bf16x3_plan(plan_code)) {      // bf16x3 codes (conv_bf16x3.h) name their tile rows and split themselves
+    const int fbm = ssp_bf16x3_plan_bm(plan_code), fks = ssp_bf16x3_plan_ksplit(plan_code);
+    pl.bm = fbm == 64 ? 64 : 128;
+    pl.ksplit = fks >= 1 ? fks : 1;
+    return pl;
+  }
   if (Cout <= 64) {
     if (Cout > 32 && Cin % 16 == 0 && ssp_option(SSP_OPT_IGEMM_VARIANT) != 50) pl.bm = 128;   // 128x64 LDS-direct tiles
     // Thin layers on small grids (the 1x1 head conv 1024 -> 20 and the 512 -> 64 route conv; at batch 1 also at 672 x 672):
@@ -609,6 +616,31 @@ int ssp_conv_igemm_launch(const float* in, const float* wt, float* out, const fl
     return ssp_wino_fused_launch(a, B, H, W, prof_kind, stream);
   }
   if (ssp_wino_plan_tile(plan)) return wino_launch(a, B, H, W, ws, ws_floats, plan, prof_kind, stream);
+  if (ssp_bf16x3_plan(plan)) {
+    // a code that does not fit its launch is an error, never a quiet run of the fp32 kernel
+    SSP_CHECK_ARG(ssp_bf16x3_fits(a.M, Cin, Cout, R, plan),
+                  "conv (bf16x3 plan %d): needs tile rows 64 | 128, split 1..9 with >= 8 K-steps each, last digit 3, "
+                  "R 1 | 3, Cin %% 16 == 0, Cout > 32 and %% 4 == 0 (got Cin %d, Cout %d, R %d)", plan, Cin, Cout, R);
+    const int bm = ssp_bf16x3_plan_bm(plan), ks = ssp_bf16x3_plan_ksplit(plan);
+    a.ksplit = ks;
+    a.ws = ws;
+    if (ks > 1) {
+      SSP_CHECK_ARG(ldout % 4 == 0 && (((uintptr_t)out) & 15) == 0, "conv: split-K output must be 16-byte aligned with ldout %% 4 == 0");
+      SSP_CHECK_ARG(ws != nullptr && (((uintptr_t)ws) & 15) == 0 && ws_floats >= (int64_t)ks * a.M * Cout,
+                    "conv: this plan runs split-K x%d and needs a workspace of %lld floats (ssp_conv_workspace_floats)", ks,
+                    (long long)ks * a.M * Cout);
+    }
+    SspProfScope prof(prof_kind, stream, 2.0 * (double)a.M * Cout * (double)(R * R * Cin));
+    if (int rc = ssp_bf16x3_launch(a, bm, prof_kind == SSP_PROF_CONV_DGRAD, stream)) return rc;
+    if (ks > 1) {
+      const int rt = (stats == nullptr && a.bn_partial == nullptr && a.M <= 16384) ? 16 : bm;
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ssp_cdiv(a.M, rt), ssp_cdiv(Cout, 64)), dim3(256), 0, stream, ws, ks, out, ldout,
+                         bias, stats, a.M, Cout, rt, accumulate, escale, act_slope, 0, a.bn_raw, a.bn_ld, a.bn_scale,
+                         a.bn_shift, a.bn_mean, a.bn_invstd, a.bn_slope, a.bn_partial, a.bn_nslot, ssp_cdiv(a.M, bm));
+      SSP_CHECK_LAUNCH("splitk_reduce");
+    }
+    return SSP_OK;
+  }
   IgemmPlan pl = select_plan(a.M, Cin, Cout, R, plan);
   if (Cout <= 64 && pl.ksplit > 1 &&
       (ws == nullptr || ws_floats < (int64_t)pl.ksplit * a.M * Cout || ldout % 4 != 0 || (((uintptr_t)out) & 15) != 0))

@@ -6,6 +6,7 @@
 
 #include "../../include/ssp_hip.h"
 #include "conv_wino.h"
+#include "conv_bf16x3.h"
 
 // ---- kernels' host launchers (defined next to the kernels) ----
 int ssp_conv_tile_m(int M, int Cin, int Cout, int R, int plan);
@@ -254,6 +255,10 @@ int64_t ssp_conv_workspace_floats(int B, int H, int W, int Cin, int Cout, int R,
   if (ssp_wino_plan_fused(plan)) return 0;      // V and M stay on the chip
   if (const int tile = ssp_wino_plan_tile(plan)) return ssp_wino_ws_floats(B, H, W, Cin, Cout, tile);      // V + M planes
   return ssp_conv_ws_floats(B * H * W, Cin, Cout, R, plan);
+}
+int ssp_conv_bf16x3_fits(int B, int H, int W, int Cin, int Cout, int R, int plan) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return ssp_bf16x3_fits((int64_t)B * H * W, Cin, Cout, R, plan);
 }
 int ssp_wino_filter_transform_t(const float* w9, float* U, int rows, int K, int tile, void* stream) {
   return ssp_wino_filter_launch(w9, U, rows, K, tile, (hipStream_t)stream);

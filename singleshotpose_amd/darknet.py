@@ -82,6 +82,7 @@ class Darknet(nn.Module):
         self._flat_grads = {}       # device -> flat gradient buffer shared by every plan's backward (engine.Plan.backward)
         self._bn_epoch = 0          # bumped by every training-mode forward (engine.Plan: inference BN constants key)
         self._max_plans = 32
+        self._conv_math = None      # see conv_math below: None = follow SSP_CONV_MATH
         # eval forward as one captured hipGraph replay (Plan.forward_graph).  Opt-in: measured no gain on MI355X - the
         # chain is not host-bound (B=1, 672x672: 1.04 ms eager, 36 launches x ~10 us of host time; 1.10 ms replayed)
         self.graph_inference = os.environ.get('SSP_GRAPH_INFERENCE', '0') == '1'
@@ -197,6 +198,23 @@ class Darknet(nn.Module):
             else:
                 print('unknown type %s' % t)
         return models
+
+    @property
+    def conv_math(self):
+        """'fp32' (default) or 'bf16x3': the arithmetic of the direct convolutions (engine.Plan._apply_conv_math, DESIGN.md
+        section 3c).  Defaults from SSP_CONV_MATH, read when a plan is built; assigning it drops the cached plans, so one
+        model can run both ways in one process."""
+        from .engine import conv_math_env
+        return self._conv_math or conv_math_env()
+
+    @conv_math.setter
+    def conv_math(self, mode):
+        from .engine import CONV_MATHS
+        if mode not in CONV_MATHS:
+            raise ValueError("conv_math %r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
+        if mode != self.conv_math:
+            self._plans.clear()
+        self._conv_math = mode
 
     # ---- forward: one autograd node, HIP launches only ----
     def _plan(self, shape, device):

@@ -43,6 +43,23 @@ IGEMM_CANDS = (12813, 12814, 6414, 6413, 12824, 12834, 306413, 306414, 312813, 3
 IGEMM_LATENCY_CANDS = (6418, 12818, 6428, 12828, 6438)
 # GEMM tilings tried under a Winograd base (WINO / WINO4 + code)
 WINO_GEMM_CANDS = (6413, 6414, 12813, 12814)
+# bf16x3 fast mode of the direct kernel (csrc/conv_igemm_bf16x3.hip): plan codes BF16X3 + tile_rows*100 + ksplit*10 + 3.
+# Opt-in (SSP_CONV_MATH=bf16x3 / Darknet.conv_math); with the mode off no such code is ever timed, cached or run.
+BF16X3 = 6000000
+CONV_MATHS = ('fp32', 'bf16x3')
+
+
+def conv_math_of(code):
+    """'bf16x3' for a 6xxxxxx plan code, 'fp32' for every other (direct and Winograd) code."""
+    return 'bf16x3' if BF16X3 <= code < BF16X3 + 1000000 else 'fp32'
+
+
+def conv_math_env():
+    """SSP_CONV_MATH: 'fp32' (default, also when unset or empty) or 'bf16x3'."""
+    mode = os.environ.get('SSP_CONV_MATH', '') or 'fp32'
+    if mode not in CONV_MATHS:
+        raise ValueError("SSP_CONV_MATH=%r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
+    return mode
 
 
 # A layer whose data gradient AND filter gradient both run in the through-memory Winograd domain of one tile size takes the
@@ -277,6 +294,8 @@ class _ConvSpec(object):
     dgrad_adj = False              # data gradient in the adjoint form, from the filter gradient's dM (_adjoint_rule)
     ws_dgrad = 0                   # split-K workspace floats of the data-gradient plan
     fwd_fams = None                # {family: (code, ms)} the head-error budget chooses from
+    x3_fwd = x3_dgrad = 0          # bf16x3 mode: the code the tuner admitted for the launch (0 = its fp32 code stays)
+    fp32_fwd = fp32_dgrad = None   # ... and the fp32 code a substituted launch goes back to (None = not substituted)
     stats = None                   # per-tile BatchNorm partial statistics
     first_fused = False
     first_partial = first_wpart = None     # fused first block: BatchNorm / filter-gradient partials
@@ -307,6 +326,15 @@ class Plan(object):
         self.net = net
         self.B, self.H, self.W = B, H, W
         self.device = device
+        # conv math of this plan, fixed when it is built: the model's attribute (Darknet.conv_math), else SSP_CONV_MATH.
+        # The record of what the mode did (Plan._apply_conv_math): layers = {layer: (forward code, data-gradient code)} of
+        # the blocks that run a bf16x3 launch, head_deviation = what those add at the head (fraction of its range),
+        # taken_back = layers the head budget sent back to fp32
+        mode = getattr(net, 'conv_math', None) or conv_math_env()
+        if mode not in CONV_MATHS:
+            raise ValueError("conv_math %r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
+        self.conv_math = dict(mode=mode, layers={}, head_deviation=0.0, taken_back=[])
+        self._cm_done = False
         blocks = net.blocks
         self.shapes = layer_shapes(blocks, W, H)  # (w, h, c) per layer
         nl = len(blocks) - 1
@@ -726,6 +754,7 @@ class Plan(object):
     def head_budget_stale(self):
         if self._head_budget_done:
             self._head_budget_done = False
+            self._conv_math_revert()         # (bf16x3 mode: its substitutions are redone after the budget, see forward)
             for k in [k for k in _HEAD_BUDGET_CACHE if k[:3] == (self.B, self.H, self.W) and k[-1] == id(self.net)]:
                 _HEAD_BUDGET_CACHE.pop(k, None)
             # (a pinned decision read from SSP_TUNE_CACHE belongs to the weights it was measured on, too)
@@ -754,6 +783,125 @@ class Plan(object):
         now = self._bn_gains()
         r = (now / self._hb_gains.clamp_min(1e-30)).clamp_min(1e-30)
         return bool(((r > 2.0) | (r < 0.5)).any())
+
+    # ------------------------------------------------------------------ bf16x3 fast mode (SSP_CONV_MATH / Darknet.conv_math)
+    # The tuner and the head budget decide first, exactly as with the mode off (so the Winograd decisions are measured
+    # against an fp32 reference); then every forward and data-gradient launch that ended on a DIRECT code and that the
+    # kernel fits is moved to a bf16x3 code: with the tuner on the one Plan._autotune timed faster than the launch's fp32
+    # code and verified (cs.x3_fwd / cs.x3_dgrad), with SSP_AUTOTUNE=0 the code with the tile rows and split of the
+    # library's own plan.  Filter gradients, the first block, stride-2 blocks and Winograd launches stay fp32.
+    def _x3_default(self, cs, which):
+        K, N = (cs.cinp, cs.cout) if which == 'fwd' else (cs.coutp, cs.cin)
+        args = (self.B, cs.H, cs.W, K, N, cs.k)
+        bm = min(_lib.query('ssp_conv_stats_tile_m', *(args + (0,))), 128)
+        ks = _lib.query('ssp_conv_workspace_floats', *(args + (0,))) // (cs.M * N)
+        for k_ in (min(max(ks, 1), 9), 1):
+            code = BF16X3 + bm * 100 + k_ * 10 + 3
+            if _lib.query('ssp_conv_bf16x3_fits', *(args + (code,))):
+                return code
+        return 0
+
+    def _conv_math_record(self):
+        self.conv_math['layers'] = {i: (cs.plan_fwd, cs.plan_dgrad) for i, cs in sorted(self.convs.items())
+                                    if 'bf16x3' in (conv_math_of(cs.plan_fwd), conv_math_of(cs.plan_dgrad))}
+
+    def _conv_math_revert(self):
+        """Every substituted launch back on its fp32 code (what the head budget measures, and measures against)."""
+        fwd = [cs for cs in self.convs.values() if cs.fp32_fwd is not None]
+        dgrad = [cs for cs in self.convs.values() if cs.fp32_dgrad is not None]
+        for cs in fwd:
+            cs.plan_fwd, cs.fp32_fwd = cs.fp32_fwd, None
+            self._size_layer(cs)
+        for cs in dgrad:
+            cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
+        if dgrad:
+            self._dgrad_sizes()
+        if fwd or dgrad:
+            self._fit_workspace()
+            self._graph = None           # a captured inference chain holds the old codes
+            self._conv_math_record()
+
+    def _apply_conv_math(self, training):
+        """The forward substitutions and their budget: one forward on the live batch measures the head deviation d the
+        substituted launches add against the head before them (fraction of its range); while
+        sqrt(head_budget.head_deviation^2 + d^2) exceeds SSP_HEAD_ERR_BUDGET the substitution nearest the network input
+        is taken back (the amplification is largest there), one forward per step.  Runs where the
+        head budget runs (the plan's first training batch, and again on its re-measurement triggers), or - a plan that
+        only ever infers - on its first forward, in that forward's mode."""
+        self._cm_done = True
+        rec = self.conv_math
+        if rec['mode'] != 'bf16x3':
+            return
+        self._conv_math_revert()
+        rec.update(layers={}, head_deviation=0.0, taken_back=[])
+        subs = []
+        for ind, cs in sorted(self.convs.items()):
+            if cs.first or cs.stride != 1 or wino_tile(cs.plan_fwd):
+                continue
+            code = cs.x3_fwd if self._tune else self._x3_default(cs, 'fwd')
+            if code:
+                subs.append((cs, code))
+
+        def assign(cs, code):
+            if code:
+                cs.fp32_fwd, cs.plan_fwd = cs.plan_fwd, code
+            else:
+                cs.plan_fwd, cs.fp32_fwd = cs.fp32_fwd, None
+            self._size_layer(cs)
+            self._fit_workspace()
+
+        budget = float(os.environ.get('SSP_HEAD_ERR_BUDGET', '3.5e-5'))
+        if subs and budget > 0:
+            o = self.out_act
+
+            def head():
+                if training:
+                    self._forward_body(True, False, False, bn_force=True)
+                else:
+                    self._forward_body(False, False, False)
+                return o.t[o.off:o.off + self.B * o.H * o.W * o.ld].clone()
+            base = (self.head_budget or {}).get('head_deviation', 0.0)
+            base = base if base == base else 0.0          # (a pinned record without a measured figure)
+            mom, self.bn_momentum = self.bn_momentum, 0.0
+            try:
+                ref = head()
+                den = max(float(ref.abs().max()), 1e-30)
+                for cs, code in subs:
+                    assign(cs, code)
+                while True:
+                    d = float((head() - ref).abs().max()) / den
+                    if not subs or (base * base + d * d) ** 0.5 <= budget:      # (false for NaN: everything goes back)
+                        break
+                    cs, _ = subs.pop(0)
+                    assign(cs, 0)
+                    rec['taken_back'].append(cs.ind)
+                rec['head_deviation'] = d
+            finally:
+                self.bn_momentum = mom
+        else:
+            for cs, code in subs:
+                assign(cs, code)
+        self._graph = None
+        if self._dgrad_fallback:         # the data-gradient choices exist already (a re-measurement): same layers there
+            self._conv_math_dgrad()
+            self._dgrad_sizes()
+        self._conv_math_record()
+
+    def _conv_math_dgrad(self):
+        """The data-gradient substitutions (Plan._prepare_backward, after the tuner): the layers the head budget took back
+        keep fp32 in both directions."""
+        rec = self.conv_math
+        if rec['mode'] != 'bf16x3':
+            return
+        for ind, cs in sorted(self.convs.items()):
+            if cs.fp32_dgrad is not None:
+                cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
+            if cs.first or cs.stride != 1 or wino_tile(cs.plan_dgrad) or ind in rec['taken_back']:
+                continue
+            code = cs.x3_dgrad if self._tune else self._x3_default(cs, 'dgrad')
+            if code:
+                cs.fp32_dgrad, cs.plan_dgrad = cs.plan_dgrad, code
+        self._conv_math_record()
 
     def _sync_codes(self, stage):
         """Multi-GPU: adopt rank 0's plan codes (singleshotpose_amd.dist.sync_plans installs the hook on the model).
@@ -784,6 +932,8 @@ class Plan(object):
                 t = (2 if v == WGRAD_FUSED else v) if wg else wino_tile(v)
                 if t and (not wino_on or t not in tiles or ((v == WGRAD_FUSED if wg else wino_fused(v)) and not fused_on)):
                     ok = False
+                if not wg and conv_math_of(v) == 'bf16x3' and self.conv_math['mode'] != 'bf16x3':
+                    ok = False       # a bf16x3 code and this rank's mode is off: like a Winograd code it switched off
         all_ok = getattr(fn, 'all_ok', None)
         if all_ok is not None:
             ok = all_ok(ok)
@@ -792,9 +942,15 @@ class Plan(object):
             cs = self.convs[i]
             if stage == 0:
                 if vals[k] != cs.plan_fwd:
+                    # (an adopted bf16x3 code keeps this rank's fp32 code to go back to; an adopted fp32 code needs none)
+                    own = cs.fp32_fwd if cs.fp32_fwd is not None else cs.plan_fwd
+                    cs.fp32_fwd = own if conv_math_of(vals[k]) == 'bf16x3' else None
                     cs.plan_fwd = vals[k]
                     self._size_layer(cs)
             else:
+                if vals[k] != cs.plan_dgrad:
+                    own = cs.fp32_dgrad if cs.fp32_dgrad is not None else cs.plan_dgrad
+                    cs.fp32_dgrad = own if conv_math_of(vals[k]) == 'bf16x3' else None
                 cs.plan_dgrad = vals[k]
                 w = vals[len(order) + k]
                 if w != cs.wgrad_wino:
@@ -804,6 +960,8 @@ class Plan(object):
                     cs.wino_ws = None
         if stage == 0:
             self._fit_workspace()
+        if self.conv_math['mode'] == 'bf16x3':
+            self._conv_math_record()
 
     def _fit_workspace(self):
         need = max([1] + [cs.ws_fwd for cs in self.convs.values()] + [cs.ws_dgrad for cs in self.convs.values()])
@@ -899,6 +1057,9 @@ class Plan(object):
             return
         self._dgrad_tuned = tune
         self._dgrad_fallback = True
+        for cs in self.convs.values():       # (bf16x3 mode: the choices below start from the fp32 codes)
+            if cs.fp32_dgrad is not None:
+                cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
         if self._tune and tune:
             self._autotune('dgrad')
             self._tune_wgrad()
@@ -913,8 +1074,17 @@ class Plan(object):
                 code = _TUNE_CACHE.get(key, 0)
                 cs.plan_dgrad = code if _TUNE_VERIFIED.get(key) == code and (not wino_tile(code) or wino_on) else 0
                 cs.wgrad_wino = 0
+                cs.fp32_dgrad = None
+                xkey = ('dgrad-bf16x3',) + key[1:]
+                xcode = _TUNE_CACHE.get(xkey, 0)
+                cs.x3_dgrad = xcode if xcode and _TUNE_VERIFIED.get(xkey) == xcode else 0
+        self._conv_math_dgrad()              # bf16x3 mode: the direct data-gradient launches the kernel fits
         if tune:
             self._sync_codes(1)              # multi-GPU: ... and rank 0's data- / filter-gradient choices
+        self._dgrad_sizes()
+
+    def _dgrad_sizes(self):
+        """What follows from the data-gradient plan codes: split-K workspace, BatchNorm-backward fusion buffers."""
         for cs in self.convs.values():
             cs.ws_dgrad = 0 if (cs.first or cs.stride == 2) else _lib.query(
                 'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
@@ -1354,6 +1524,83 @@ class Plan(object):
                                          [(cs.raw, cs.ldraw, 0, cs.cout), wslice], None,
                                          (lambda code=code: prep_d(wino_tile(code))) if wino_tile(code) else None)
                 cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
+        if self.conv_math['mode'] == 'bf16x3':
+            # bf16x3 mode, after (and apart from) the decisions above: the launch's direct fp32 code against the bf16x3 codes
+            # (tile rows 64 / 128 x the split depths the direct list tries at this grid size), timed the same way, near-ties
+            # to the fp32 code, verified against plan 0 at the direct family's 1e-5.  Keys of their own ('fwd-bf16x3' /
+            # 'dgrad-bf16x3'): nothing above reads them.  Plan._apply_conv_math / _conv_math_dgrad make the substitutions.
+            def timed(launch, code):
+                try:
+                    launch(code)
+                    ts = []
+                    for _ in range(2):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        launch(code)
+                        e1.record()
+                        e1.synchronize()
+                        ts.append(e0.elapsed_time(e1))
+                    return min(ts)
+                except _lib.SspError:
+                    return None
+
+            def x3_pick(cs, K, N, launch, xkey, fp32_code):
+                if xkey in _TUNE_CACHE:
+                    return _TUNE_CACHE[xkey]
+                mn = cs.M * _pad4(N)
+                splits = (1,) if mn > (1 << 25) else (1, 2, 3) + ((4, 5, 6, 8, 9) if mn <= (1 << 21) else ())
+                best, best_t = 0, timed(launch, fp32_code)
+                for bm in (128, 64):
+                    for ks in splits:
+                        code = BF16X3 + bm * 100 + ks * 10 + 3
+                        if not _lib.query('ssp_conv_bf16x3_fits', B, cs.H, cs.W, K, N, cs.k, code):
+                            continue
+                        t = timed(launch, code)
+                        if t is not None and (best_t is None or t < best_t * 0.985):
+                            best, best_t = code, t
+                _TUNE_CACHE[xkey] = best
+                return best
+
+            for cs in elig:
+                if cs.first:
+                    continue
+                if which == 'fwd' and _lib.query('ssp_conv_bf16x3_fits', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, BF16X3 + 12813):
+                    wop = cs.conv.weight if cs.cinp == cs.cin else self._wbuf(cs)
+                    xkey = ('fwd-bf16x3', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, cs.inp.ld, cs.ldraw, bool(cs.bn), _tune_tag())
+
+                    def launch(code, cs=cs, wop=wop):
+                        call('ssp_conv_fwd', cs.inp.ptr, wop.data_ptr(), cs.raw.data_ptr(), None,
+                             stats.data_ptr() if cs.bn else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
+                             cs.k, 0, code, ws.data_ptr(), max_ws, st)
+
+                    def bn_of(code, cs=cs):
+                        tm = _lib.query('ssp_conv_stats_tile_m', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
+                        nt = _lib.query('ssp_conv_stats_tiles', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
+                        tmp = torch.zeros(8, cs.coutp, **f32)
+                        tmp[0].fill_(1.0)
+                        tmp[3].fill_(1.0)
+                        call('ssp_bn_fwd_finalize', stats.data_ptr(), nt, tm, cs.M, cs.cout,
+                             tmp[0].data_ptr(), tmp[1].data_ptr(), tmp[2].data_ptr(), tmp[3].data_ptr(), BN_MOMENTUM,
+                             BN_EPS, tmp[4].data_ptr(), tmp[5].data_ptr(), tmp[6].data_ptr(), tmp[7].data_ptr(), st)
+                        return [tmp[4, :cs.cout].clone(), tmp[5, :cs.cout].clone()]
+
+                    # the direct code the layer runs when it ends on one (now, or when the head budget moves it there)
+                    fp32_code = (cs.fwd_fams or {}).get(0, (0 if wino_tile(cs.plan_fwd) else cs.plan_fwd, None))[0]
+                    a = cs.inp
+                    ops_ = [(a.t, a.ld, a.off % a.ld, cs.cinp)] + ([] if wop is cs.conv.weight else [wop])
+                    cs.x3_fwd = admitted(x3_pick(cs, cs.cinp, cs.cout, launch, xkey, fp32_code), xkey, launch,
+                                         lambda cs=cs: cs.raw, ops_, bn_of if cs.bn else None)
+                if which == 'dgrad' and not wino_tile(cs.plan_dgrad) and _lib.query(
+                        'ssp_conv_bf16x3_fits', B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, BF16X3 + 12813):
+                    xkey = ('dgrad-bf16x3',) + self._dgrad_key(cs)[1:]
+                    wslice = self._dpack[cs.doff:cs.doff + cs.cinp * cs.k * cs.k * cs.coutp]
+
+                    def launch(code, cs=cs):
+                        call('ssp_conv_dgrad', cs.raw.data_ptr(), _ptr(self._dpack, cs.doff), gscratch.data_ptr(), B, cs.H,
+                             cs.W, cs.coutp, cs.cin, cs.ldraw, cs.inp.ld, cs.k, 0, code, ws.data_ptr(), max_ws, st)
+
+                    cs.x3_dgrad = admitted(x3_pick(cs, cs.coutp, cs.cin, launch, xkey, cs.plan_dgrad), xkey, launch,
+                                           lambda cs=cs: gscratch[:cs.M * cs.inp.ld], [(cs.raw, cs.ldraw, 0, cs.cout), wslice])
         torch.cuda.synchronize()
         if len(_TUNE_CACHE) != n_known:
             _tune_cache_save()
@@ -1385,9 +1632,13 @@ class Plan(object):
                 if drifted:
                     self.head_budget_stale()
         if training and need_grad and not self._head_budget_done:
+            self._conv_math_revert()         # (bf16x3 mode: the budget below measures fp32 launches against fp32 launches)
             self._apply_head_budget()        # on the plan's first training batch, after load_weights, and when the BatchNorm
                                              # gains drifted (network-level rounding budget)
+            self._apply_conv_math(True)      # bf16x3 mode: the direct launches it fits, under the same budget
             self._sync_codes(0)              # multi-GPU: every rank runs rank 0's forward codes
+        elif not self._cm_done:
+            self._apply_conv_math(training)  # a plan that has not trained yet: on its first forward
         # (The whole training step as two captured hipGraphs was built and measured in round 4 - profiles/r04_step_graph.txt:
         # a replayed two-stream chain of ~300 nodes is SLOWER than launching it, 9.1 ms against 6.0 ms at batch 8 - and
         # removed in round 5: it mirrored this method's host-side state by hand.  Inference keeps its graph, forward_graph.)

@@ -160,6 +160,9 @@ def run_cases(args, dev, st, B):
                     continue
                 if (op == 'dgrad' and name == 'l0') or (op == 'wfilt' and not wino) or (op == 'wgrad' and plan != int(args.plans.split(',')[0])) or (op == 'wgradw' and wsw is ws):
                     continue
+                if 6000000 <= plan < 7000000 and op in ('fwd', 'dgrad') and not _lib.query(      # bf16x3 codes: a misfit is an error
+                        'ssp_conv_bf16x3_fits', B, H, W, *((Cin, Cout) if op == 'fwd' else (coutp, Cin)), R, plan):
+                    continue
                 fn = fns[op]
                 for _ in range(3):
                     fn()

@@ -1,11 +1,23 @@
 #!/usr/bin/env python
 """Prints the autotuned igemm plan of every conv launch of cfg/yolo-pose.cfg at a given batch / size
-(plan code = tail*100000 + tile_rows*100 + ksplit*10 + ring_slots; 0 = library heuristic; 9xxxxxx = Winograd F(2x2), 8xxxxxx = Winograd F(4x4))."""
+(plan code = tail*100000 + tile_rows*100 + ksplit*10 + ring_slots; 0 = library heuristic; 9xxxxxx = Winograd F(2x2), 8xxxxxx = Winograd F(4x4),
+7xxxxxx = on-chip F(2x2), 6xxxxxx = bf16x3 (6000000 + tile_rows*100 + ksplit*10 + 3; only with SSP_CONV_MATH=bf16x3))."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from singleshotpose_amd.darknet import Darknet
+from singleshotpose_amd.engine import conv_math_of, wino_fused, wino_tile
+
+
+def family(code):
+    if conv_math_of(code) == 'bf16x3':
+        return 'bf16x3'
+    if wino_fused(code):
+        return 'F(2x2) on-chip'
+    return 'F(%dx%d)' % (wino_tile(code), wino_tile(code)) if wino_tile(code) else 'direct'
+
+
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 416
 m = Darknet(os.path.join(ROOT, 'cfg', 'yolo-pose.cfg')).cuda().train()
@@ -13,5 +25,7 @@ x = torch.rand(B, 3, S, S, device='cuda')
 m(x).sum().backward()
 plan = list(m._plans.values())[0]
 for ind, cs in sorted(plan.convs.items()):
-    print('layer %2d  %4dx%-4d %4d->%-4d k%d  fwd %7d  dgrad %7d  wgrad %s' % (ind, cs.H, cs.W, cs.cin, cs.cout, cs.k, cs.plan_fwd, cs.plan_dgrad,
-                                                                              ('winograd F(%dx%d)' % (cs.wgrad_wino, cs.wgrad_wino)) if getattr(cs, 'wgrad_wino', 0) else 'direct'))
+    print('layer %2d  %4dx%-4d %4d->%-4d k%d  fwd %7d %-14s  dgrad %7d %-14s  wgrad %s' % (
+        ind, cs.H, cs.W, cs.cin, cs.cout, cs.k, cs.plan_fwd, family(cs.plan_fwd), cs.plan_dgrad, family(cs.plan_dgrad),
+        ('winograd F(%dx%d)' % (cs.wgrad_wino, cs.wgrad_wino)) if getattr(cs, 'wgrad_wino', 0) else 'direct'))
+print('conv math: %r' % (plan.conv_math,))
