@@ -465,6 +465,21 @@ int ssp_region_match_multi(const float* out, const float* target, float* rows, i
                            int nW, int num_keypoints, float conf_thresh, int only_objectness, int im_width, int im_height,
                            void* stream);
 
+/* Label-free multi-object detection: the same selection as ssp_region_match_multi, for a LIST OF CLASSES instead of an
+ * image's label rows, one workgroup per image, every image on its own.  classes: nQ class ids (int32, on the device),
+ * or NULL for every class in order (nQ must then equal nC, slot q is class q); an id may repeat, each slot gets its
+ * class's row.  For image b and slot q of class c the result is the box get_multi_region_boxes(out[b:b+1], ...,
+ * correspondingclass = c, only_objectness) followed by valid_multi.py:118-123 selects: source, key, tie rule and
+ * fallback chain exactly as described above (the two kernels call the same device functions).
+ *   rows[b][q][2K+3] = {2K coords as ssp_region_decode_all, det_conf, class confidence, class id}
+ *   meta[b][q][2]    = {source, scan-order key (cy*nW + cx)*nA + anchor}
+ * source 0 (an all-zero row, key -1): c outside [0, nC), or a head whose det_conf is NaN everywhere.  Every element of
+ * rows and meta is written by every launch; nQ is not capped.  Refused before the launch: num_keypoints != 9, more
+ * than 4096 cells (nA * nH * nW) per image, nQ < 1, nC outside 1..65535, a null out / rows / meta, classes == NULL
+ * with nQ != nC. */
+int ssp_region_detect_multi(const float* out, const int* classes, float* rows, int* meta, int nB, int nA, int nC, int nH,
+                            int nW, int num_keypoints, int nQ, float conf_thresh, int only_objectness, void* stream);
+
 /* ---- PnP (utils.py:86-100: cv2.solvePnP ITERATIVE + cv2.Rodrigues) ----------------------------------------- */
 /* batched: pts3d [n][N][3], pts2d [n][N][2], K [n][9] (row-major) doubles on the device -> Rt [n][12] = R (9) | t (3) */
 int ssp_pnp_batched(const double* pts3d, const double* pts2d, const double* K, double* Rt, int n, int N, int max_iter,

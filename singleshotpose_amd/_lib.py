@@ -108,6 +108,7 @@ _SIGS = {
     "ssp_region_decode_argmax": [P, P, I, I, I, I, I, I, I, P],
     "ssp_region_decode_all": [P, P, I, I, I, I, I, I, P],
     "ssp_region_match_multi": [P, P, P, P, I, I, I, I, I, I, F, I, I, I, P],
+    "ssp_region_detect_multi": [P, P, P, P, I, I, I, I, I, I, I, F, I, P],
     "ssp_pnp_batched": [P, P, P, P, I, I, I, P],
     "ssp_prof_enable": [I],
     "ssp_prof_nkinds": [],

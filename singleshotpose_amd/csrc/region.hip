@@ -388,6 +388,75 @@ __device__ __forceinline__ void match_better(float& d, int& k, float od, int ok)
 
 #define SSP_MATCH_NO_KEY 0x7fffffff
 
+// ---- device code shared by region_match_multi_kernel and region_detect_multi_kernel ------------------------------
+// base: offset of channel 0 of the cell (image, anchor, cy, cx) in the head; hw: the channel stride.
+
+// det_conf, logit maximum, soft-max denominator and arg-max class of one cell (region_decode_all_kernel's expressions)
+template <int K>
+__device__ __forceinline__ void match_cell_scores(const float* __restrict__ out, int64_t base, int64_t hw, int nC,
+                                                  float& det, float& mx, float& se, int& arg) {
+  det = sigmoidf_(out[base + (2 * K) * hw]);
+  mx = -INFINITY;
+  arg = 0;
+  for (int q = 0; q < nC; ++q) {
+    float z = out[base + (2 * K + 1 + q) * hw];
+    if (z > mx) { mx = z; arg = q; }
+  }
+  se = 0.f;
+  for (int q = 0; q < nC; ++q) se += expf(out[base + (2 * K + 1 + q) * hw] - mx);
+}
+
+// soft-max probability of class c given the cell's logit maximum and denominator (region_decode_all_kernel's softmax[c])
+template <int K>
+__device__ __forceinline__ float match_class_prob(const float* __restrict__ out, int64_t base, int64_t hw, int c, float mx,
+                                                  float se) {
+  return expf(out[base + (2 * K + 1 + c) * hw] - mx) / se;
+}
+
+// Selection among the kept cells of class c: the calling thread scans keys first, first + stride, ...; on return every
+// lane of its wave holds the wave's best (det_conf, key) - (-inf, SSP_MATCH_NO_KEY) when no scanned cell is kept.
+// Whole waves only (shuffles).
+__device__ __forceinline__ void match_select_wave(const float* s_det, const float* s_se, const unsigned short* s_cid,
+                                                  int ncell, int first, int stride, int c, float conf_thresh,
+                                                  int only_objectness, float& bd, int& bk) {
+  bd = -INFINITY;
+  bk = SSP_MATCH_NO_KEY;
+  for (int key = first; key < ncell; key += stride) {
+    float d = s_det[key];
+    float conf = only_objectness ? d : d * (1.f / s_se[key]);
+    if (conf > conf_thresh && (int)s_cid[key] == c && d > bd) { bd = d; bk = key; }   // keys ascend: first maximum kept
+  }
+  for (int off = 32; off > 0; off >>= 1) match_better(bd, bk, __shfl_xor(bd, off), __shfl_xor(bk, off));
+}
+
+// The reference's fallback box: the LAST cell taken by the sequential rule `det > max_conf and p_c > max_cls_conf` walked
+// in scan order.  One whole wave walks the cells 64 at a time: the first lane that passes under the current
+// (max_conf, max_cls_conf) is exactly the next cell the sequential walk takes (the lanes before it failed under
+// thresholds that only rise), so one ballot per taken cell replays the chain exactly.  p_of(key) is the class
+// probability of cell key; the next 64 are fetched while this block's ballots run.  Returns the key of the last cell
+// taken (m, q: its det_conf and class probability), -1 when the walk takes none (NaN everywhere).
+template <typename PF>
+__device__ __forceinline__ int match_fallback_chain(const float* s_det, int ncell, int lane, PF p_of, float& m, float& q) {
+  m = -1.f;                          // max_conf = -1
+  q = -9223372036854775807.f;        // max_cls_conf = -sys.maxsize
+  int taken = -1;
+  float pn = lane < ncell ? p_of(lane) : 0.f;
+  for (int base = 0; base < ncell; base += 64) {
+    const int key = base + lane;
+    const bool valid = key < ncell;
+    const float d = valid ? s_det[key] : 0.f, p = pn;
+    pn = key + 64 < ncell ? p_of(key + 64) : 0.f;
+    while (true) {
+      const unsigned long long pass = __ballot(valid && d > m && p > q);
+      if (pass == 0ull) break;
+      const int f = __ffsll((long long)pass) - 1;
+      m = __shfl(d, f); q = __shfl(p, f);
+      taken = base + f;
+    }
+  }
+  return taken;
+}
+
 // Multi-object validation matching: for every ground truth (b, t) of class c the box valid_multi.py:110-123 selects
 // from get_multi_region_boxes(output[b:b+1], ..., correspondingclass = c) (utils_multi.py:266-382), each image on its
 // own.  One workgroup per image:
@@ -401,6 +470,8 @@ __device__ __forceinline__ void match_better(float& d, int& k, float od, int ok)
 //      taken cell replays the chain exactly -> source 2; a chain that never takes a cell (NaN) -> source 0;
 //   4. one fixed row per ground-truth slot: rows[b][t] = {2K coords, det_conf, cls_conf, cls, match},
 //      meta[b][t] = {source, scan-order key}.
+// Steps 1-3 are the shared device functions above (match_cell_scores, match_select_wave, match_class_prob,
+// match_fallback_chain); region_detect_multi_kernel below runs the same ones for a list of classes.
 template <int K>
 __global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __restrict__ out,
                                                                  const float* __restrict__ target, int nA, int nC, int nH,
@@ -434,15 +505,10 @@ __global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __
   for (int key = tid; key < ncell; key += 256) {
     int an = key % nA, rem = key / nA;
     int64_t base = ((int64_t)(b * nA + an) * nCh) * hw + rem;
-    s_det[key] = sigmoidf_(out[base + (2 * K) * hw]);
-    float mx = -INFINITY;
-    int arg = 0;
-    for (int q = 0; q < nC; ++q) {
-      float z = out[base + (2 * K + 1 + q) * hw];
-      if (z > mx) { mx = z; arg = q; }
-    }
-    float se = 0.f;
-    for (int q = 0; q < nC; ++q) se += expf(out[base + (2 * K + 1 + q) * hw] - mx);
+    float det, mx, se;
+    int arg;
+    match_cell_scores<K>(out, base, hw, nC, det, mx, se, arg);
+    s_det[key] = det;
     s_se[key] = se;
     s_cid[key] = (unsigned short)arg;
   }
@@ -464,14 +530,9 @@ __global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __
   for (int t = 0; t < ngt; ++t) {      // every branch below is uniform over the workgroup
     const int c = gt_cls[t];
     if (gt_first[t] != t || c < 0 || c >= nC) continue;
-    float bd = -INFINITY;
-    int bk = SSP_MATCH_NO_KEY;
-    for (int key = tid; key < ncell; key += 256) {
-      float d = s_det[key];
-      float conf = only_objectness ? d : d * (1.f / s_se[key]);
-      if (conf > conf_thresh && (int)s_cid[key] == c && d > bd) { bd = d; bk = key; }   // keys ascend: first maximum kept
-    }
-    for (int off = 32; off > 0; off >>= 1) match_better(bd, bk, __shfl_xor(bd, off), __shfl_xor(bk, off));
+    float bd;
+    int bk;
+    match_select_wave(s_det, s_se, s_cid, ncell, tid, 256, c, conf_thresh, only_objectness, bd, bk);
     if (lane == 0) { s_wd[wid] = bd; s_wk[wid] = bk; }
     __syncthreads();
     bd = s_wd[0]; bk = s_wk[0];
@@ -487,24 +548,12 @@ __global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __
           float z = out[base + (2 * K + 1 + q) * hw];
           if (z > mx) mx = z;
         }
-        s_pc[key] = expf(out[base + (2 * K + 1 + c) * hw] - mx) / s_se[key];
+        s_pc[key] = match_class_prob<K>(out, base, hw, c, mx, s_se[key]);
       }
       __syncthreads();
       if (wid == 0) {
-        float m = -1.f, q = -9223372036854775807.f;   // max_conf = -1, max_cls_conf = -sys.maxsize
-        int taken = -1;
-        for (int base = 0; base < ncell; base += 64) {
-          const int key = base + lane;
-          const bool valid = key < ncell;
-          const float d = valid ? s_det[key] : 0.f, p = valid ? s_pc[key] : 0.f;
-          while (true) {
-            const unsigned long long pass = __ballot(valid && d > m && p > q);
-            if (pass == 0ull) break;
-            const int f = __ffsll((long long)pass) - 1;
-            m = __shfl(d, f); q = __shfl(p, f);
-            taken = base + f;
-          }
-        }
+        float m, q;
+        const int taken = match_fallback_chain(s_det, ncell, lane, [&](int key) { return s_pc[key]; }, m, q);
         if (lane == 0 && taken >= 0) { res_src[t] = 2; res_key[t] = taken; res_det[t] = m; res_cc[t] = q; }
       }
     }
@@ -536,6 +585,108 @@ __global__ void __launch_bounds__(256) region_match_multi_kernel(const float* __
       mo[0] = src; mo[1] = key;
     }
   }
+}
+
+// Label-free multi-object detection: region_match_multi_kernel's selection for a list of nQ classes instead of the
+// classes of an image's label rows (classes == nullptr: slot q is class q).  One workgroup per image:
+//   1. every cell's det_conf, logit maximum, soft-max sum and arg-max class go to LDS once (match_cell_scores);
+//      4 arrays at SSP_MAX_CELLS = 56 KB of static LDS, no per-class probability array and no result arrays;
+//   2. no barrier after that: wave w owns the slots w, w + 4, ... and works through them on its own.  Per slot:
+//      match_select_wave over all cells (source 1), else match_fallback_chain (source 2, or 0 when it takes no cell),
+//      then the wave decodes the selected cell's 2K coordinates (one per lane) and writes rows[b][q] / meta[b][q]
+//      straight to global memory - every slot is written, a class outside [0, nC) as source 0.
+// What it costs.  On a real frame most queried classes are absent, so the chain is the common path here (in validation
+// it is the rare one).  Per absent class a wave reads every cell's det_conf from LDS and its class logit from global
+// memory once - ncell strided 4-byte loads, L2 hits after step 1, the next 64 issued before the current block's
+// ballots - plus one ballot + two shuffles per taken cell; the taken cells are the records of a random sequence, about
+// ln(ncell) + a few of them (~10 at 845 cells), so the walk is bound by the ceil(ncell / 64) dependent load rounds,
+// not by the ballots.  Keeping the logit maximum in LDS saves the nC loads per cell the match kernel spends to find it
+// again; four chains run at once, one per wave, so 13 classes take four rounds.  The selection scan costs ceil(ncell /
+// 64) LDS rounds per slot whether or not the class is present; a repeated class id is simply computed again.
+template <int K>
+__global__ void __launch_bounds__(256) region_detect_multi_kernel(const float* __restrict__ out,
+                                                                  const int* __restrict__ classes, int nA, int nC, int nH,
+                                                                  int nW, int nQ, float conf_thresh, int only_objectness,
+                                                                  float* __restrict__ rows, int* __restrict__ meta) {
+  constexpr int RW = 2 * K + 3;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nCh = 2 * K + 1 + nC;
+  const int64_t hw = (int64_t)nH * nW;
+  const int ncell = nA * nH * nW;
+
+  __shared__ float s_det[SSP_MAX_CELLS];             // det_conf, indexed by the scan-order key
+  __shared__ float s_mx[SSP_MAX_CELLS];              // largest class logit
+  __shared__ float s_se[SSP_MAX_CELLS];              // soft-max denominator: cls_max_conf = 1 / se
+  __shared__ unsigned short s_cid[SSP_MAX_CELLS];    // arg-max class
+
+  for (int key = tid; key < ncell; key += 256) {
+    int an = key % nA, rem = key / nA;
+    int64_t base = ((int64_t)(b * nA + an) * nCh) * hw + rem;
+    float det, mx, se;
+    int arg;
+    match_cell_scores<K>(out, base, hw, nC, det, mx, se, arg);
+    s_det[key] = det;
+    s_mx[key] = mx;
+    s_se[key] = se;
+    s_cid[key] = (unsigned short)arg;
+  }
+  __syncthreads();
+
+  for (int slot = wid; slot < nQ; slot += 4) {       // every branch below is uniform over the wave
+    const int c = classes ? classes[slot] : slot;
+    int src = 0, key = -1;
+    float det = 0.f, cc = 0.f;
+    if (c >= 0 && c < nC) {
+      float bd;
+      int bk;
+      match_select_wave(s_det, s_se, s_cid, ncell, lane, 64, c, conf_thresh, only_objectness, bd, bk);
+      if (bk != SSP_MATCH_NO_KEY) {
+        src = 1; key = bk; det = s_det[bk]; cc = 1.f / s_se[bk];
+      } else {
+        float m, q;
+        const int taken = match_fallback_chain(s_det, ncell, lane, [&](int k) {
+          const int an = k % nA, rem = k / nA;
+          return match_class_prob<K>(out, ((int64_t)(b * nA + an) * nCh) * hw + rem, hw, c, s_mx[k], s_se[k]);
+        }, m, q);
+        if (taken >= 0) { src = 2; key = taken; det = m; cc = q; }
+      }
+    }
+    float* o = rows + ((int64_t)b * nQ + slot) * RW;
+    int* mo = meta + ((int64_t)b * nQ + slot) * 2;
+    if (lane < 2 * K) {
+      float v = 0.f;
+      if (src != 0) {
+        const int an = key % nA, rem = key / nA;
+        const int j = rem / nW, i = rem % nW;
+        v = out[((int64_t)(b * nA + an) * nCh) * hw + rem + lane * hw];
+        if (lane < 2) v = sigmoidf_(v);            // only keypoint 0 goes through the sigmoid (decode_cell)
+        v = (lane & 1) ? (v + (float)j) / (float)nH : (v + (float)i) / (float)nW;
+      }
+      o[lane] = v;
+    } else if (lane == 2 * K) {
+      o[2 * K] = det;
+      o[2 * K + 1] = cc;
+      o[2 * K + 2] = src != 0 ? (float)c : 0.f;
+      mo[0] = src; mo[1] = key;
+    }
+  }
+}
+
+int ssp_region_detect_multi_launch(const float* out, const int* classes, float* rows, int* meta, int nB, int nA, int nC,
+                                   int nH, int nW, int num_keypoints, int nQ, float conf_thresh, int only_objectness,
+                                   hipStream_t stream) {
+  SSP_CHECK_ARG(num_keypoints == 9, "region_detect_multi: only num_keypoints == 9 is built (got %d)", num_keypoints);
+  SSP_CHECK_ARG(out && rows && meta, "region_detect_multi: null buffer");
+  SSP_CHECK_ARG(nB >= 1 && nA >= 1 && nH >= 1 && nW >= 1, "region_detect_multi: empty head");
+  SSP_CHECK_ARG(nC >= 1 && nC <= 65535, "region_detect_multi: need 1..65535 classes (got %d)", nC);
+  SSP_CHECK_ARG((int64_t)nA * nH * nW <= SSP_MAX_CELLS, "region_detect_multi: more than %d cells per image", SSP_MAX_CELLS);
+  SSP_CHECK_ARG(nQ >= 1, "region_detect_multi: need at least one queried class (got nQ = %d)", nQ);
+  SSP_CHECK_ARG(classes || nQ == nC, "region_detect_multi: classes == NULL means every class: nQ must be %d (got %d)", nC, nQ);
+  SspProfScope prof(SSP_PROF_REGION, stream, 0.0);
+  hipLaunchKernelGGL((region_detect_multi_kernel<9>), dim3(nB), dim3(256), 0, stream, out, classes, nA, nC, nH, nW, nQ,
+                     conf_thresh, only_objectness, rows, meta);
+  SSP_CHECK_LAUNCH("region_detect_multi");
+  return SSP_OK;
 }
 
 int ssp_region_match_multi_launch(const float* out, const float* target, float* rows, int* meta, int nB, int nA, int nC,

@@ -130,6 +130,9 @@ int ssp_region_decode_all_launch(const float* out, float* rows, int nB, int nA, 
 int ssp_region_match_multi_launch(const float* out, const float* target, float* rows, int* meta, int nB, int nA, int nC,
                                   int nH, int nW, int num_keypoints, float conf_thresh, int only_objectness, int im_width,
                                   int im_height, hipStream_t stream);
+int ssp_region_detect_multi_launch(const float* out, const int* classes, float* rows, int* meta, int nB, int nA, int nC,
+                                   int nH, int nW, int num_keypoints, int nQ, float conf_thresh, int only_objectness,
+                                   hipStream_t stream);
 int ssp_pnp_batched_launch(const double* pts3d, const double* pts2d, const double* K, double* Rt, int n, int N,
                            int max_iter, hipStream_t stream);
 
@@ -558,6 +561,12 @@ int ssp_region_match_multi(const float* out, const float* target, float* rows, i
                            void* stream) {
   return ssp_region_match_multi_launch(out, target, rows, meta, nB, nA, nC, nH, nW, num_keypoints, conf_thresh,
                                        only_objectness, im_width, im_height, (hipStream_t)stream);
+}
+
+int ssp_region_detect_multi(const float* out, const int* classes, float* rows, int* meta, int nB, int nA, int nC, int nH,
+                            int nW, int num_keypoints, int nQ, float conf_thresh, int only_objectness, void* stream) {
+  return ssp_region_detect_multi_launch(out, classes, rows, meta, nB, nA, nC, nH, nW, num_keypoints, nQ, conf_thresh,
+                                        only_objectness, (hipStream_t)stream);
 }
 
 int ssp_pnp_batched(const double* pts3d, const double* pts2d, const double* K, double* Rt, int n, int N, int max_iter,

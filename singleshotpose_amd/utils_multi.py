@@ -13,6 +13,10 @@ truth on the device, one fused ssp_pnp_batched launch and one ssp_pose_errors la
 Given one mesh per class ({class id: vertices}) every ground truth is scored against its own object model
 (ssp_pose_errors_models), the symmetric classes with ADD-S as well (ssp_adds_errors); summarize_multi turns the result
 into the per-class accuracies the reference's validators print.
+
+detect_multi_region_boxes / detect_multi_batched are the same selection WITHOUT labels, for a trained network on new
+images: ssp_region_detect_multi selects the box of every queried class of every image in one launch (the device code of
+ssp_region_match_multi), one ssp_pnp_batched launch turns all of them into poses, one copy returns the result.
 """
 import collections
 import collections.abc
@@ -296,6 +300,127 @@ def evaluate_multi_batched(output, target, conf_thresh, num_classes, num_keypoin
                      packed[:, o:o + 9].reshape(-1, 3, 3).copy(), packed[:, o + 9:o + 12].reshape(-1, 3, 1).copy(),
                      packed[:, o + 12:o + 21].reshape(-1, 3, 3).copy(), packed[:, o + 21:o + 24].reshape(-1, 3, 1).copy(),
                      packed[:, o + 24:o + 24 + ncol].copy())
+
+
+MultiDetect = collections.namedtuple('MultiDetect', 'boxes source key classes')
+MultiPoses = collections.namedtuple('MultiPoses', 'image cls source key det_conf cls_conf corners2D_pr R_pr t_pr')
+
+
+def _class_list(classes, num_classes, who):
+    """A host iterable of class ids (None: every class) as a list of ints; ValueError on an empty list or an id outside
+    [0, num_classes) - nothing here touches the GPU."""
+    if classes is None:
+        return list(range(int(num_classes)))
+    cl = [int(c) for c in classes]
+    if len(cl) == 0:
+        raise ValueError("%s: the list of classes is empty" % who)
+    bad = [c for c in cl if not 0 <= c < num_classes]
+    if bad:
+        raise ValueError("%s: class %s is outside [0, %d)" % (who, bad, num_classes))
+    return cl
+
+
+def detect_multi_region_boxes(output, conf_thresh, num_classes, num_keypoints, num_anchors, classes=None,
+                              only_objectness=0):
+    """The box of every queried class on every image, WITHOUT labels, in one launch and with no copy to the host.
+
+    output: the raw head (B, nA*(2K+1+nC), H, W) on the device; classes: a host iterable of class ids (an id may repeat,
+    any order), or None for all num_classes of them.  For image b and class c the result is what
+    get_multi_region_boxes(output[b:b+1], ..., correspondingclass=c, only_objectness) followed by the validator's
+    best-det_conf selection (valid_multi.py:118-123) yields - the rows match_multi_region_boxes returns for a ground truth
+    of class c, from the same device code.  Returns device tensors, nQ = len(classes):
+      boxes   (B, nQ, 2K+3) float32  2K normalised corner coordinates, det_conf, class confidence, class
+      source  (B, nQ) int32          1 a kept cell of class c (conf > conf_thresh and c is its arg-max class); 2 the
+                                     reference's fallback box: NOTHING of class c passed the threshold, the object is
+                                     probably not in the image; 0 no result (det_conf NaN everywhere), the row is all zero
+      key     (B, nQ) int32          scan-order index (cy*W + cx)*nA + anchor of the selected cell, -1 when source is 0
+      classes (nQ,) int32            the queried class of every column
+    Images are independent (see match_multi_region_boxes).  An empty list and an id outside [0, num_classes) raise
+    ValueError before the GPU is touched; a CPU `output` raises RuntimeError (no CPU fallback)."""
+    K = num_keypoints
+    cl = _class_list(classes, num_classes, "detect_multi_region_boxes")
+    out = _head_f32(output, num_classes, K, num_anchors, "detect_multi_region_boxes")
+    B, h, w = out.size(0), out.size(2), out.size(3)
+    nQ = len(cl)
+    if classes is None:
+        cls_dev, cls_ptr = torch.arange(nQ, dtype=torch.int32, device=out.device), None      # NULL: slot q is class q
+    else:
+        cls_dev = torch.tensor(cl, dtype=torch.int32).to(out.device)
+        cls_ptr = cls_dev.data_ptr()
+    rows = torch.empty(B, nQ, 2 * K + 3, dtype=torch.float32, device=out.device)
+    meta = torch.empty(B, nQ, 2, dtype=torch.int32, device=out.device)
+    _lib.call('ssp_region_detect_multi', out.data_ptr(), cls_ptr, rows.data_ptr(), meta.data_ptr(), B, num_anchors,
+              num_classes, h, w, K, nQ, float(conf_thresh), 1 if only_objectness else 0,
+              torch.cuda.current_stream().cuda_stream)
+    return MultiDetect(rows, meta[..., 0], meta[..., 1], cls_dev)
+
+
+def detect_multi_batched(output, conf_thresh, num_classes, num_keypoints, anchors, num_anchors, vertices,
+                         intrinsic_calibration, im_width, im_height, classes=None, only_objectness=0, keep_fallback=True):
+    """From the raw head of a batch of NEW images (no labels) to one 6D pose per image and object class.
+
+    detect_multi_region_boxes, then on the device: the corners denormalised in float32 (x * im_width, y * im_height),
+    ONE PnP launch over all B * nQ (image, class) problems - each with the object points of its own class (centroid 0 +
+    the 8 corners of get_3D_corners(vertices[c])) and K rounded to float32, as evaluate_multi_batched does - and one
+    device->host copy.  Rows without a result (source 0) still occupy a problem slot, fed with fixed finite corners,
+    and are dropped afterwards: the launch shape depends on B and nQ only.
+
+    vertices: {class id: (3|4, N) mesh}; classes: a host iterable of class ids, default the mapping's sorted keys;
+    intrinsic_calibration: (3,3), or (B,3,3) with one camera per image.  keep_fallback=False also drops the source 2
+    rows (nothing of that class passed the threshold - see detect_multi_region_boxes).  Returns numpy arrays over the
+    n surviving (image, class) pairs, in (image, class-list) order: image, cls, source, key (n,) ints; det_conf,
+    cls_conf (n,) float32; corners2D_pr (n,9,2) float32 pixels; R_pr (n,3,3), t_pr (n,3,1) float64.
+    A `vertices` that is no mapping, an empty mapping, a mesh that is not (3|4, N), a queried class without a mesh or
+    outside [0, num_classes), an empty class list and intrinsics of another shape raise ValueError before the GPU is
+    touched; a CPU `output` raises RuntimeError."""
+    K = num_keypoints
+    if not isinstance(vertices, collections.abc.Mapping):
+        raise ValueError("detect_multi_batched needs one object model per class: pass vertices as {class id: mesh}")
+    mclasses, _, _, objs, _ = _class_models(vertices, None)
+    cl = _class_list(mclasses if classes is None else classes, num_classes, "detect_multi_batched")
+    missing = [c for c in cl if c not in mclasses]
+    if missing:
+        raise ValueError("detect_multi_batched: class %s has no object model" % missing)
+    B = 1 if output.dim() == 3 else output.size(0)
+    K32 = np.array(np.asarray(intrinsic_calibration.cpu() if torch.is_tensor(intrinsic_calibration)
+                              else intrinsic_calibration), dtype='float32')
+    if K32.shape not in ((3, 3), (B, 3, 3)):
+        raise ValueError("intrinsic_calibration must be (3,3) or (B,3,3) = (%d,3,3), got %s" % (B, K32.shape))
+    d = detect_multi_region_boxes(output, conf_thresh, num_classes, K, num_anchors, cl, only_objectness)
+    dev = d.boxes.device
+    nQ = len(cl)
+    n = B * nQ
+    # one upload of the floats: the object points of the queried classes, the camera(s), the pixel scale and the
+    # stand-in corners of the rows without a result (a 3 x 3 grid inside the image: finite and not degenerate)
+    which = [mclasses.index(c) for c in cl]
+    grid = np.array([[im_width * (1 + i) / 4.0, im_height * (1 + j) / 4.0] for j in range(3) for i in range(3)])
+    blob = torch.as_tensor(np.concatenate((objs[which].reshape(-1), K32.astype(np.float64).reshape(-1), grid.reshape(-1),
+                                           [float(im_width), float(im_height)]))).to(dev)
+    o1 = nQ * K * 3
+    o2 = o1 + K32.size
+    p3 = blob[:o1].reshape(nQ, K, 3).repeat(B, 1, 1).contiguous()                # problem b * nQ + q: class cl[q]
+    Kt = blob[o1:o2].reshape(-1, 1, 3, 3).expand(-1, nQ, 3, 3) if K32.ndim == 3 else blob[o1:o2].reshape(1, 3, 3)
+    Kt = Kt.reshape(-1, 3, 3).expand(n, 3, 3).contiguous()
+    standin = blob[o2:o2 + 2 * K].reshape(1, K, 2)
+    scale = blob[o2 + 2 * K:].to(torch.float32)
+    src = d.source.reshape(n)
+    c_pr = d.boxes[..., :2 * K].reshape(n, K, 2) * scale
+    p2 = torch.where((src != 0).reshape(n, 1, 1), c_pr.to(torch.float64), standin).contiguous()
+    Rt = pnp_device(p3, p2, Kt)
+    packed = torch.cat((src.to(torch.float64).unsqueeze(1), d.key.reshape(n, 1).to(torch.float64),
+                        d.boxes[..., 2 * K:2 * K + 2].reshape(n, 2).to(torch.float64),
+                        c_pr.reshape(n, 2 * K).to(torch.float64), Rt), dim=1).cpu().numpy()
+    keep = packed[:, 0] != 0
+    if not keep_fallback:
+        keep &= packed[:, 0] != 2
+    image = np.repeat(np.arange(B, dtype=np.int64), nQ)[keep]
+    cls = np.tile(np.asarray(cl, dtype=np.int64), B)[keep]
+    packed = packed[keep]
+    o = 4 + 2 * K
+    return MultiPoses(image, cls, packed[:, 0].astype(np.int64), packed[:, 1].astype(np.int64),
+                      packed[:, 2].astype(np.float32), packed[:, 3].astype(np.float32),
+                      packed[:, 4:o].astype(np.float32).reshape(-1, K, 2), packed[:, o:o + 9].reshape(-1, 3, 3).copy(),
+                      packed[:, o + 9:o + 12].reshape(-1, 3, 1).copy())
 
 
 def summarize_multi(ev, diameters, px=5.0, add_frac=0.1, cm=0.05, deg=5.0):

@@ -4,6 +4,8 @@ forward at 672x672 (valid.py's test size), decode, batched PnP, batched pose err
 multi-object validator (eval_multi: evaluate_multi_batched against today's per-ground-truth host route).
 Prints one JSON object; numbers go to DESIGN.md section 3.  `infer_bench.py eval_multi` runs that line alone;
 `infer_bench.py pnp` the batched PnP line alone;
+`infer_bench.py detect_multi` times the label-free multi-object detector (detect_multi_batched, all 13 classes) against
+the per-image, per-class host route;
 `infer_bench.py adds` times ADD-S and the per-class validator."""
 import json
 import os
@@ -77,6 +79,60 @@ def eval_multi(res):
     n = len(batched().image)
     res['eval_multi_b64_13x13_2gt_batched'] = {'us': round(timed(batched, 20) * 1e6, 1), 'ground_truths': n}
     res['eval_multi_b64_13x13_2gt_per_gt_host_route'] = {'us': round(timed(per_gt, 2, warm=1) * 1e6, 1), 'ground_truths': per_gt()}
+
+
+def detect_multi(res):
+    """B=64, 5x13x13 head, all 13 classes, one mesh per class, no labels.  `batched`: one detect_multi_batched call
+    (detect kernel, one PnP launch over the 832 problems, one copy); `select_only`: detect_multi_region_boxes alone,
+    synchronised.  `per_class_host_route`: the label-free route without them - per image and class a batch-1
+    get_multi_region_boxes, the selection loop of valid_multi.py:118-123 and one pnp call."""
+    from singleshotpose_amd import utils_multi as UM
+    B, nA, nC, K, grid, thresh = 64, 5, 13, 9, 13, 0.05
+    anchors = [1.4820, 2.2412, 2.0501, 3.1265, 2.3946, 4.6891, 3.1018, 3.9910, 3.4879, 5.8851]
+    g = torch.Generator().manual_seed(0)
+    head = torch.randn(B, nA, 2 * K + 1 + nC, grid, grid, generator=g)
+    head[:, :, 2 * K] -= 3.0                              # a few dozen cells per image above the threshold
+    head = head.view(B, -1, grid, grid).cuda()
+    rs = np.random.RandomState(0)
+    half = np.array([0.038, 0.039, 0.046])
+    verts = np.concatenate(((rs.uniform(-1, 1, (5841, 3)) * half).T, np.ones((1, 5841))), axis=0)
+    meshes = {c: np.concatenate((verts[:3] * (1.0 + 0.1 * c), verts[3:]), axis=0) for c in range(nC)}
+    Kc = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.5704, 242.0489], [0.0, 0.0, 1.0]])
+    objs = {c: np.array(np.concatenate((np.zeros((3, 1)), UM.get_3D_corners(meshes[c])[:3, :]), axis=1).T, dtype='float32')
+            for c in range(nC)}
+    K32 = np.array(Kc, dtype='float32')
+
+    def batched():
+        return UM.detect_multi_batched(head, thresh, nC, K, anchors, nA, meshes, Kc, 640, 480)
+
+    def select_only(th=thresh):
+        d = UM.detect_multi_region_boxes(head, th, nC, K, nA)
+        torch.cuda.synchronize()
+        return d
+
+    def per_class():
+        poses = 0
+        for b in range(B):
+            for c in range(nC):
+                boxes = UM.get_multi_region_boxes(head[b:b + 1], thresh, nC, K, anchors, nA, c, only_objectness=0)[0]
+                best = -sys.maxsize
+                for bx in boxes:
+                    if bx[2 * K] > best and bx[2 * K + 2] == c:
+                        best, box_pr = bx[2 * K], bx
+                pr = np.array(np.reshape(box_pr[:2 * K], [-1, 2]), dtype='float32') * np.float32([640, 480])
+                UM.pnp(objs[c], pr, K32)
+                poses += 1
+        return poses
+
+    p = batched()
+    res['detect_multi_b64_13x13_13cls_batched'] = {'us': round(timed(batched, 20) * 1e6, 1), 'poses': len(p.image),
+                                                   'fallback_rows': int((p.source == 2).sum())}
+    res['detect_multi_b64_13x13_13cls_select_only'] = {'us': round(timed(select_only, 50) * 1e6, 1)}
+    # the same launch at a threshold nothing passes: every one of the 832 rows walks the fallback chain
+    res['detect_multi_b64_13x13_13cls_select_only_all_fallback'] = {
+        'us': round(timed(lambda: select_only(0.9), 50) * 1e6, 1), 'fallback_rows': int((select_only(0.9).source == 2).sum())}
+    res['detect_multi_b64_13x13_13cls_per_class_host_route'] = {'us': round(timed(per_class, 1, warm=1) * 1e6, 1),
+                                                                'poses': B * nC}
 
 
 def adds(res):
@@ -172,9 +228,9 @@ def pnp(res):
 
 
 def main():
-    if sys.argv[1:] in (['eval_multi'], ['adds'], ['pnp']):
+    if sys.argv[1:] in (['eval_multi'], ['detect_multi'], ['adds'], ['pnp']):
         res = {}
-        {'eval_multi': eval_multi, 'adds': adds, 'pnp': pnp}[sys.argv[1]](res)
+        {'eval_multi': eval_multi, 'detect_multi': detect_multi, 'adds': adds, 'pnp': pnp}[sys.argv[1]](res)
         print(json.dumps(res))
         return
     from singleshotpose_amd import utils as U
