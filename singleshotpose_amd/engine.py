@@ -29,38 +29,12 @@ import torch
 from . import _lib
 from .cfg import layer_shapes, resolve_layers
 
-WINO = 9000000       # plan codes WINO + tile_rows*100 + 10 + ring_slots: Winograd F(2x2, 3x3) evaluation (csrc/conv_wino.hip)
-WINO4 = 8000000      # ... and WINO4 + the same: F(4x4, 3x3)
-WGRAD_FUSED = 12     # `tile` value of ssp_conv_wgrad_wino_t: F(2x2) filter gradient with both transforms on the chip
-WINOF = 7000001      # F(2x2, 3x3) with the transform domain kept on the chip (csrc/conv_wino_fused.hip): one persistent launch,
-                     # no workspace; same transformed filters, same arithmetic (and error family) as a WINO plan
-# Direct plan codes Plan._autotune times (include/ssp_hip.h: tail*100000 + tile_rows*100 + ksplit*10 + ring_slots): tile
-# rows x split-K x ring depth; 2xxxxx / 3xxxxx / 4xxxxx = hybrid launches (whole resident waves un-split, the tiles of the
-# last partial wave split 2 / 3 / 4 ways over K)
-IGEMM_CANDS = (12813, 12814, 6414, 6413, 12824, 12834, 306413, 306414, 312813, 312814, 206413, 212814,
-               12823, 6423, 6424, 206414, 212813, 406413, 406414, 412813)
-# ring depth 8 = the latency form of the kernel (one workgroup per CU, 7 chunks in flight)
-IGEMM_LATENCY_CANDS = (6418, 12818, 6428, 12828, 6438)
-# GEMM tilings tried under a Winograd base (WINO / WINO4 + code)
-WINO_GEMM_CANDS = (6413, 6414, 12813, 12814)
-# bf16x3 fast mode of the direct kernel (csrc/conv_igemm_bf16x3.hip): plan codes BF16X3 + tile_rows*100 + ksplit*10 + 3.
-# Opt-in (SSP_CONV_MATH=bf16x3 / Darknet.conv_math); with the mode off no such code is ever timed, cached or run.
-BF16X3 = 6000000
-CONV_MATHS = ('fp32', 'bf16x3')
-
-
-def conv_math_of(code):
-    """'bf16x3' for a 6xxxxxx plan code, 'fp32' for every other (direct and Winograd) code."""
-    return 'bf16x3' if BF16X3 <= code < BF16X3 + 1000000 else 'fp32'
-
-
-def conv_math_env():
-    """SSP_CONV_MATH: 'fp32' (default, also when unset or empty) or 'bf16x3'."""
-    mode = os.environ.get('SSP_CONV_MATH', '') or 'fp32'
-    if mode not in CONV_MATHS:
-        raise ValueError("SSP_CONV_MATH=%r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
-    return mode
-
+from .tuning import (BF16X3, BN_EPS, BN_MOMENTUM, CONV_MATHS, IGEMM_CANDS, IGEMM_LATENCY_CANDS, TUNE_REJECTED,  # noqa: F401
+                     WGRAD_FUSED, WINO, WINO4, WINO_GEMM_CANDS, WINOF, _HEAD_BUDGET_CACHE, _HEAD_BUDGET_PINNED, _TUNE_CACHE,
+                     _TUNE_CACHE_FILE, _TUNE_FAMILY, _TUNE_VERIFIED, _TUNE_VERIFIED_ALSO, _pad4, _tune_cache_load, _tune_cache_save,
+                     _tune_tag, conv_math_env, conv_math_of, form_allowed, knobs, tune_convs, tune_wgrad, wino_fused, wino_tile, x3_key)
+# (tuning.py holds the plan codes, the process-wide tune state and the passes that choose the codes; bench.py, the tests and
+# the tools reach them as engine.X - the same objects)
 
 # A layer whose data gradient AND filter gradient both run in the through-memory Winograd domain of one tile size takes the
 # data gradient in its adjoint form (ssp_conv_dgrad_adj): it contracts the dM = A dY A^T planes the filter gradient
@@ -68,79 +42,9 @@ def conv_math_env():
 # not a tuner choice, no plan code, not part of the tune tag.  SSP_WINO_SHARE_DM=0 (read once) switches it off for A/Bs.
 _SHARE_DM = os.environ.get('SSP_WINO_SHARE_DM', '1') != '0'
 
-
-def _tune_tag():
-    """Candidate-set tag, part of every tune-cache key: a cache entry written before a family of candidates existed, or in a
-    process that had it switched off (SSP_WINOGRAD=0, SSP_WINO_TILES, SSP_WINO_MIN_CHANNELS), must not keep that family
-    from ever being timed - and must not hand a Winograd code to a process that switched it off."""
-    if os.environ.get('SSP_WINOGRAD', '1') == '0':
-        return 'r5-direct'
-    return 'r6-w%s-c%s-%s-f%s' % (os.environ.get('SSP_WINO_TILES', '2,4'), os.environ.get('SSP_WINO_MIN_CHANNELS', '128'),
-                                  os.environ.get('SSP_WINO4_MIN_CHANNELS', '64'),
-                                  os.environ.get('SSP_WINO_FUSED', '1') + os.environ.get('SSP_WGRAD_FUSED_PREFER', '') +
-                                  os.environ.get('SSP_ONCHIP_PREFER', '') + os.environ.get('SSP_ONCHIP_CREDIT_MS', ''))
-
-
-def wino_fused(code):
-    """True for the on-chip F(2x2) plan codes (7xxxxxx)."""
-    return 7000000 <= code < 8000000
-
-
-def wino_tile(code):
-    """Output-tile edge of a plan code: 2 / 4 for a Winograd plan, 0 for a direct one (ssp_conv_plan_wino_tile).  The on-chip
-    F(2x2) codes count as tile 2: same filter transform, same error family."""
-    return 2 if (WINO <= code < WINO + 1000000 or wino_fused(code)) else (4 if WINO4 <= code < WINO4 + 1000000 else 0)
-BN_EPS = 1e-4        # darknet.py:157
-BN_MOMENTUM = 0.1    # nn.BatchNorm2d default
-
-
 # bumped by writers that change parameter memory without going through torch ops (singleshotpose_amd.optim.SGD's
 # fused launch): part of the packed-filter cache key
 _WEIGHTS_EPOCH = [0]
-# autotuned igemm plan per launch shape, shared by every Plan of the process: multi-scale training (dataset.py:66-90
-# draws a new resolution every 10 batches) revisits the same ~20 shapes, each is timed once
-_TUNE_CACHE = {}
-# ... and per FAMILY of that launch (0 = direct kernels, 2 / 4 = Winograd F(2x2) / F(4x4)): launch shape -> {family: (fastest code
-# of the family, its time in ms)} - what the error budget of the forward plans chooses from (Plan._apply_head_budget)
-_TUNE_FAMILY = {}
-_HEAD_BUDGET_CACHE = {}        # (plan shape, tag, budget, model) -> record: a rebuilt plan re-measures nothing
-_HEAD_BUDGET_PINNED = {}       # (plan shape, tag, budget) -> {layer: forward plan code}: decisions read from / written to the
-                               # SSP_TUNE_CACHE file - a process started with that file runs the SAME plan set without measuring
-                               # (profiled runs hold training steps only; multi-process jobs can share one file)
-_TUNE_VERIFIED = {}            # launch shape -> the plan code(s) that passed verify-after-tune in this process
-_TUNE_VERIFIED_ALSO = set()    # (launch shape, code) pairs verified besides the chosen one (the other families' fastest codes)
-TUNE_REJECTED = []             # (shape key, plan code) pairs verify-after-tune refused
-_TUNE_CACHE_FILE = [None]      # SSP_TUNE_CACHE=<json file>: loaded once, rewritten whenever a new shape was timed
-
-
-def _tune_cache_load():
-    path = os.environ.get('SSP_TUNE_CACHE')
-    if not path or _TUNE_CACHE_FILE[0] == path:
-        return
-    _TUNE_CACHE_FILE[0] = path
-    if os.path.isfile(path):
-        import json
-        with open(path) as f:
-            for k, v in json.load(f).items():
-                if k.startswith('fam|'):
-                    _TUNE_FAMILY.setdefault(tuple(json.loads(k[4:])), {int(f_): (int(c), t) for f_, (c, t) in v.items()})
-                elif k.startswith('budget|'):      # a pinned error-budget decision (layer -> forward code) of a plan shape
-                    _HEAD_BUDGET_PINNED.setdefault(tuple(json.loads(k[7:])), {int(i): int(c) for i, c in v.items()})
-                else:
-                    _TUNE_CACHE.setdefault(tuple(json.loads(k)), int(v))
-
-
-def _tune_cache_save():
-    path = _TUNE_CACHE_FILE[0]
-    if path:
-        import json
-        tmp = path + '.tmp.%d' % os.getpid()
-        with open(tmp, 'w') as f:
-            out = {json.dumps(list(k)): v for k, v in _TUNE_CACHE.items()}
-            out.update({'fam|' + json.dumps(list(k)): {str(f_): [c, t] for f_, (c, t) in v.items()} for k, v in _TUNE_FAMILY.items()})
-            out.update({'budget|' + json.dumps(list(k)): {str(i): c for i, c in v.items()} for k, v in _HEAD_BUDGET_PINNED.items()})
-            json.dump(out, f, indent=0, sort_keys=True)
-        os.replace(tmp, path)
 
 
 def _storage_refs(t):
@@ -197,10 +101,6 @@ def _is_packed(wt, cinp):
 
 def _ptr(t, offset=0):
     return t.data_ptr() + 4 * offset
-
-
-def _pad4(c):
-    return (c + 3) // 4 * 4
 
 
 def choose_under_budget(table, budget):
@@ -452,7 +352,7 @@ class Plan(object):
                 else:
                     cs.out = _Act(cs.raw, 0, c, cs.H, cs.W, cs.coutp)
                 cs.out.flat = t == 'connected'
-                cs.plan_fwd = cs.plan_dgrad = 0     # explicit igemm plan codes (0 = library heuristic), see _autotune
+                cs.plan_fwd = cs.plan_dgrad = 0     # explicit igemm plan codes (0 = library heuristic), see tuning.tune_convs
                 # per-channel vectors: mean, invstd, scale, shift, c1, c2, dgamma, dbeta
                 cs.vec = torch.zeros(8, cs.coutp, **f32)
                 if not cs.bn:
@@ -546,9 +446,9 @@ class Plan(object):
         self._dgrad_tuned = False
         self._dgrad_fallback = False     # Plan.backward's no-tuning fallback made its choices (once per plan)
         self.bn_partial = torch.empty(_lib.query('ssp_bn_bwd_blocks') * 2 * max(cs.coutp for cs in self.convs.values()), **f32)
-        self._tune = device.type == 'cuda' and os.environ.get('SSP_AUTOTUNE', '1') != '0'
+        self._tune = device.type == 'cuda' and knobs().autotune
         if self._tune:
-            self._autotune('fwd')
+            tune_convs(self, 'fwd')
         # statistics / split-K workspaces follow the (tuned or heuristic) plan of each launch
         for cs in self.convs.values():
             M = cs.M
@@ -662,7 +562,7 @@ class Plan(object):
         self._hb_gains = None
         self._hb_gains_after_forward = False
         self._hb_checked = self.generation
-        budget = float(os.environ.get('SSP_HEAD_ERR_BUDGET', '3.5e-5'))
+        budget = knobs().head_budget
         if budget <= 0 or not self._tune:
             return
         cand = [cs for cs in self.convs.values() if wino_tile(cs.plan_fwd) and 0 in (cs.fwd_fams or {})]
@@ -787,7 +687,7 @@ class Plan(object):
     # ------------------------------------------------------------------ bf16x3 fast mode (SSP_CONV_MATH / Darknet.conv_math)
     # The tuner and the head budget decide first, exactly as with the mode off (so the Winograd decisions are measured
     # against an fp32 reference); then every forward and data-gradient launch that ended on a DIRECT code and that the
-    # kernel fits is moved to a bf16x3 code: with the tuner on the one Plan._autotune timed faster than the launch's fp32
+    # kernel fits is moved to a bf16x3 code: with the tuner on the one tuning.tune_convs timed faster than the launch's fp32
     # code and verified (cs.x3_fwd / cs.x3_dgrad), with SSP_AUTOTUNE=0 the code with the tile rows and split of the
     # library's own plan.  Filter gradients, the first block, stride-2 blocks and Winograd launches stay fp32.
     def _x3_default(self, cs, which):
@@ -850,7 +750,7 @@ class Plan(object):
             self._size_layer(cs)
             self._fit_workspace()
 
-        budget = float(os.environ.get('SSP_HEAD_ERR_BUDGET', '3.5e-5'))
+        budget = knobs().head_budget
         if subs and budget > 0:
             o = self.out_act
 
@@ -922,15 +822,13 @@ class Plan(object):
         # fall back to the library's heuristic plans (code 0) for this stage - deterministic and the same everywhere.
         ok = got[:5] == head and len(got) == len(head) + len(mine)
         if ok:
-            wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
-            tiles = tuple(int(t) for t in os.environ.get('SSP_WINO_TILES', '2,4').split(',') if t)
-            fused_on = os.environ.get('SSP_WINO_FUSED', '1') != '0'
+            kn = knobs()
             for k, v in enumerate(got[5:]):
                 if v == mine[k] or v == 0:
                     continue
                 wg = stage == 1 and k >= len(order)                 # (the filter gradients' entries ARE tile sizes)
                 t = (2 if v == WGRAD_FUSED else v) if wg else wino_tile(v)
-                if t and (not wino_on or t not in tiles or ((v == WGRAD_FUSED if wg else wino_fused(v)) and not fused_on)):
+                if not form_allowed(kn, t, onchip=(v == WGRAD_FUSED if wg else wino_fused(v))):
                     ok = False
                 if not wg and conv_math_of(v) == 'bf16x3' and self.conv_math['mode'] != 'bf16x3':
                     ok = False       # a bf16x3 code and this rank's mode is off: like a Winograd code it switched off
@@ -1061,10 +959,10 @@ class Plan(object):
             if cs.fp32_dgrad is not None:
                 cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
         if self._tune and tune:
-            self._autotune('dgrad')
-            self._tune_wgrad()
+            tune_convs(self, 'dgrad')
+            tune_wgrad(self)
         elif self._tune:
-            wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
+            kn = knobs()
             for cs in self.convs.values():
                 if cs.stride != 1:      # no plan codes (and its key would be a stride-1 layer's of the same shape)
                     continue
@@ -1072,10 +970,10 @@ class Plan(object):
                 # (the code that was verified, not just the key: a cached Winograd code that SSP_WINOGRAD=0 kept out of
                 # this process must not come back through this fallback)
                 code = _TUNE_CACHE.get(key, 0)
-                cs.plan_dgrad = code if _TUNE_VERIFIED.get(key) == code and (not wino_tile(code) or wino_on) else 0
+                cs.plan_dgrad = code if _TUNE_VERIFIED.get(key) == code and form_allowed(kn, wino_tile(code), wino_fused(code)) else 0
                 cs.wgrad_wino = 0
                 cs.fp32_dgrad = None
-                xkey = ('dgrad-bf16x3',) + key[1:]
+                xkey = x3_key(key)
                 xcode = _TUNE_CACHE.get(xkey, 0)
                 cs.x3_dgrad = xcode if xcode and _TUNE_VERIFIED.get(xkey) == xcode else 0
         self._conv_math_dgrad()              # bf16x3 mode: the direct data-gradient launches the kernel fits
@@ -1103,121 +1001,6 @@ class Plan(object):
 
     def _wgrad_key(self, cs):
         return ('wgrad', self.B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw, cs.inp.ld, _tune_tag())
-
-    def _tune_wgrad(self):
-        """Filter gradients of the deep 3x3 layers: direct kernel or Winograd domain (ssp_conv_wgrad_wino_t, tile 2 or 4),
-        whichever is fastest on this shape; a Winograd form is admitted only after its result on seeded operands agrees with
-        the direct kernel's to 3e-5 of the gradient's range.  Runs before the first forward of the plan (its operands are the
-        plan's own, still empty, buffers).  The choice (0 = direct, else the tile size) is cached per launch shape like the
-        igemm plans."""
-        call = _lib.call
-        st = torch.cuda.current_stream().cuda_stream
-        wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
-        verify = os.environ.get('SSP_TUNE_VERIFY', '1') != '0'
-        tiles = tuple(int(t) for t in os.environ.get('SSP_WINO_TILES', '2,4').split(',') if t)
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(4321)
-        n_known = len(_TUNE_CACHE)
-        for cs in self.convs.values():
-            cs.wgrad_wino = 0
-            cmin = min(cs.cin, cs.cout)
-            if not (wino_on and cs.k == 3 and cs.stride == 1 and not cs.first and cs.cinp == cs.cin and
-                    cs.coutp == cs.cout and cs.cin % 16 == 0 and cs.cout % 16 == 0):
-                continue
-            # tile sizes worth timing: F(2x2) from SSP_WINO_MIN_CHANNELS (128) channels on both sides, F(4x4) from 64 ...
-            ts_ok = [t for t in tiles if cmin >= 64 and cmin >= int(os.environ.get('SSP_WINO_MIN_CHANNELS', '128') if t == 2 else
-                                                                    os.environ.get('SSP_WINO4_MIN_CHANNELS', '64')) and
-                     self.B * ((cs.H + t - 1) // t) * ((cs.W + t - 1) // t) >= 16]
-            # ... and F(2x2) with both transforms on the chip (WGRAD_FUSED: csrc/conv_wino_wgrad_fused.hip), 32-channel granularity
-            if (2 in tiles and os.environ.get('SSP_WINO_FUSED', '1') != '0' and cs.cin % 32 == 0 and cs.cout % 32 == 0 and
-                    (self.B * cs.H * cs.W + cs.W + 1) * max(cs.inp.ld, cs.ldraw) * 4 < (1 << 31)):
-                ts_ok.append(WGRAD_FUSED)
-            if not ts_ok:
-                continue
-            key = self._wgrad_key(cs)
-            wsn = {t: _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', self.B, cs.H, cs.W, cs.cinp, cs.cout, t) for t in ts_ok}
-            cached = _TUNE_CACHE.get(key)
-            if cached is not None and (cached == 0 or (cached in ts_ok and (not verify or _TUNE_VERIFIED.get(key) == cached))):
-                cs.wgrad_wino = cached
-            else:
-                ws = torch.empty(max(wsn.values()), dtype=torch.float32, device=self.device)
-                dw = [torch.zeros(cs.cout * 9 * cs.cinp, dtype=torch.float32, device=self.device) for _ in range(2)]
-                a = cs.inp
-                a.t.view(-1, a.ld)[:, a.off % a.ld:a.off % a.ld + cs.cinp].uniform_(-1.0, 1.0, generator=gen)
-                cs.raw.view(-1, cs.ldraw)[:, :cs.cout].uniform_(-1.0, 1.0, generator=gen)
-
-                def direct(out, cs=cs):
-                    call('ssp_conv_wgrad', cs.raw.data_ptr(), cs.inp.ptr, out.data_ptr(), self.B, cs.H, cs.W, cs.cinp, cs.cout,
-                         cs.ldraw, cs.inp.ld, cs.k, st)
-
-                def wino(out, t, cs=cs, ws=ws):
-                    call('ssp_conv_wgrad_wino_t', cs.raw.data_ptr(), cs.inp.ptr, out.data_ptr(), self.B, cs.H, cs.W, cs.cinp,
-                         cs.cout, cs.ldraw, cs.inp.ld, t, ws.data_ptr(), ws.numel(), st)
-
-                def timed(fn):
-                    fn(torch.empty_like(dw[0]))
-                    best = None
-                    for _ in range(3):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        fn(torch.empty_like(dw[0]))
-                        e1.record()
-                        e1.synchronize()
-                        t = e0.elapsed_time(e1)
-                        best = t if best is None else min(best, t)
-                    return best
-
-                use, t_best = 0, None
-                try:
-                    t_best = timed(direct)
-                    dw[0].zero_()
-                    direct(dw[0])
-                    den = float(dw[0].abs().max())
-                except _lib.SspError:
-                    t_best, den = None, 1.0
-                for t in ts_ok:
-                    if t_best is None:
-                        break
-                    try:
-                        tt = timed(lambda out, t=t: wino(out, t))
-                        if t == WGRAD_FUSED:
-                            # timed alone, the HBM-bound transform passes of the other Winograd forms run at full bandwidth; in the
-                            # step they share it with the data-gradient stream.  SSP_WGRAD_FUSED_PREFER (default 0.8) credits the on-chip
-                            # form (no such passes) with that difference: same-box A/B of the whole step, two interleaved rounds, 26.64 / 26.45 ms
-                            # with 1.0 (layers 4 / 6 stay on the F(4x4) chain) against 26.12 / 26.13 ms with 0.8 (profiles/r06_step_ab.txt)
-                            # Big launches only (>= SSP_ONCHIP_CREDIT_MS, 0.25 ms alone): at batch 8 the on-chip launches are 0.15 ms
-                            # of mostly fixed cost (1024 waves x 144 atomics of flush) and the credit picked them for eight layers -
-                            # 6.49 / 6.48 ms per step against 6.33 / 6.32 without it (same box)
-                            if tt >= float(os.environ.get('SSP_ONCHIP_CREDIT_MS', '0.25')):
-                                tt *= float(os.environ.get('SSP_WGRAD_FUSED_PREFER', '0.8'))
-                        if not tt < 0.985 * t_best:
-                            continue
-                        # verification pair: one accumulation each into zeroed buffers
-                        dw[1].zero_()
-                        wino(dw[1], t)
-                        err = float((dw[0] - dw[1]).abs().max())
-                        ok = err <= 3e-5 * max(den, 1e-30)
-                    except _lib.SspError:
-                        continue
-                    if not ok:
-                        TUNE_REJECTED.append((key, 'wgrad_wino%d' % t))
-                        import warnings
-                        warnings.warn("singleshotpose_amd: verify-after-tune refused the Winograd F(%dx%d) filter gradient "
-                                      "for %s" % (t, t, key))
-                        continue
-                    use, t_best = t, tt
-                _TUNE_CACHE[key] = use
-                _TUNE_VERIFIED[key] = use
-                cs.wgrad_wino = use
-                del ws, dw
-            if cs.wgrad_wino:
-                cs.wino_ws_floats = wsn[cs.wgrad_wino]
-        torch.cuda.synchronize()
-        if len(_TUNE_CACHE) != n_known:
-            _tune_cache_save()
-        # the timing / verification scratch (workspaces for the deepest candidate, gradient scratch, twin outputs) goes back
-        # to the driver: left in the caching allocator it sits reserved next to the plan's own buffers (multi-scale soak)
-        torch.cuda.empty_cache()
 
     def _dgrad_key(self, cs):
         return ('dgrad', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.ldraw, cs.inp.ld, _tune_tag())
@@ -1266,347 +1049,6 @@ class Plan(object):
             _lib.call('ssp_wino_filter_transform_adj_t' if cs.dgrad_adj else 'ssp_wino_filter_transform_t',
                       _ptr(self._dpack, cs.doff), self._wino_ud(cs, tile).data_ptr(), cs.cin, cs.coutp, tile,
                       stream.cuda_stream)
-
-    # ------------------------------------------------------------------ per-shape tile / split selection
-    def _autotune(self, which):
-        """Times the candidate igemm plans (tile rows x split-K x LDS ring depth) of every eligible conv launch of this
-        input shape on the real buffers and keeps the fastest (per-shape tile selection).
-        The library's shape heuristic is within ~5-15 % of the best choice on some layers; which plan wins depends on
-        how the grid fills the 256 CUs.  One-off cost per (B,H,W): ~1 s for yolo-pose.cfg.  SSP_AUTOTUNE=0 disables;
-        SSP_TUNE_CACHE=<file> keeps the timed choices across processes (JSON).
-
-        Verify-after-tune: a non-default plan is admitted only after its output on seeded random operands agrees with the
-        default plan's output of the same launch (max|a-b| / max|b| <= 1e-5: the plans differ in fp32 summation order
-        only) and, for BN layers, after the batch statistics finalized from its per-tile partials agree too.  A code that
-        fails is refused (plan 0 runs) and reported in `engine.TUNE_REJECTED`.  Cached choices (this process or the JSON
-        file) are re-verified once per process."""
-        B = self.B
-        call = _lib.call
-        st = torch.cuda.current_stream().cuda_stream
-        f32 = dict(dtype=torch.float32, device=self.device)
-        _tune_cache_load()
-        n_known = len(_TUNE_CACHE)
-        # tile rows x split-K x ring depth; 3xxxxx / 2xxxxx = hybrid launches (whole resident waves un-split, the tiles of
-        # the last partial wave split 3 / 2 ways over K)
-        cands = IGEMM_CANDS
-        # ring depth 8 = the latency form of the kernel (one workgroup per CU, 7 chunks in flight): only worth timing on
-        # grids that cannot give a CU several workgroups anyway (small-batch inference)
-        lat = IGEMM_LATENCY_CANDS
-        elig = [cs for cs in self.convs.values() if cs.cinp % 16 == 0 and cs.stride == 1]
-        if not elig:
-            return
-        # Winograd F(2x2, 3x3) candidates (csrc/conv_wino.hip): 16/36 of the multiplies at the price of two HBM-bound
-        # transform passes - timed against the direct plans on the 3x3 layers with >= 128 channels on both sides (with 64
-        # the tuner never picked one: the transforms of the wide maps cost more than the short-K GEMMs save; measured,
-        # profiles/r03_step_ab_winograd.txt).  SSP_WINOGRAD=0 turns them off, SSP_WINO_MIN_CHANNELS moves the threshold.
-        # F(4x4, 3x3) candidates (WINO4): 36/144 of the multiplies and 2.25 instead of 4 transform floats per pixel, so they
-        # are timed from 64 channels up (SSP_WINO_TILES=2 or =4 restricts the tile sizes tried).
-        gemm_cands = WINO_GEMM_CANDS
-        wino_on = os.environ.get('SSP_WINOGRAD', '1') != '0'
-        wino_min = int(os.environ.get('SSP_WINO_MIN_CHANNELS', '128'))
-        wino_tiles = tuple(int(t) for t in os.environ.get('SSP_WINO_TILES', '2,4').split(',') if t)
-
-        def wino_bases(cs, which):
-            """Plan-code bases (WINO / WINO4) of the Winograd forms worth timing on this launch."""
-            if not (wino_on and cs.k == 3 and not cs.first and cs.cinp == cs.cin and cs.coutp == cs.cout and
-                    cs.cin % 16 == 0 and cs.cout % 16 == 0):
-                return ()
-            bases = []
-            if 2 in wino_tiles and min(cs.cin, cs.cout) >= wino_min:
-                bases.append(WINO)
-            if 4 in wino_tiles and min(cs.cin, cs.cout) >= int(os.environ.get('SSP_WINO4_MIN_CHANNELS', '64')):
-                bases.append(WINO4)
-            return tuple(bases)
-
-        fused_on = wino_on and os.environ.get('SSP_WINO_FUSED', '1') != '0' and 2 in wino_tiles
-
-        def fused_ok(cs, which):
-            """The on-chip F(2x2) kernel (csrc/conv_wino_fused.hip) fits: 3x3, channel counts multiples of 32 on both sides of
-            the launch (forward: Cin -> Cout; data gradient: Cout -> Cin), no channel padding."""
-            return (fused_on and cs.k == 3 and not cs.first and cs.cinp == cs.cin and cs.coutp == cs.cout and
-                    cs.cin % 32 == 0 and cs.cout % 32 == 0 and B * cs.H * cs.W * max(cs.inp.ld, cs.ldraw) * 4 < (1 << 31))
-
-        def wino_codes(cs, which, small=False):
-            codes = []
-            for base in wino_bases(cs, which):
-                codes += [base + c for c in gemm_cands]
-                if small:      # small grids - batch-1 inference: also the 8-slot latency ring, as for the direct plans
-                    codes += [base + 6418, base + 12818]
-            if fused_ok(cs, which):
-                codes.append(WINOF)
-            return tuple(codes)
-        def ws_need(cs):       # split-K scratch of the deepest candidate tried on this shape (x9 small, x4 mid, none big)
-            mc = cs.M * max(cs.coutp, cs.cinp)
-            need = 9 * mc if mc <= (1 << 21) else (4 * mc if mc <= (1 << 25) else 1)
-            # ... and what the library's own heuristic (plan 0: the reference launch of verify-after-tune) asks for: it may
-            # split K on a shape the candidate list does not (batch 64 at 832 x 832: the 26 x 26 layers, x3)
-            need = max(need, _lib.query('ssp_conv_workspace_floats', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, 0))
-            if not cs.first:
-                need = max(need, _lib.query('ssp_conv_workspace_floats', B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, 0))
-            for base in wino_bases(cs, 'fwd') + wino_bases(cs, 'dgrad'):
-                need = max(need, _lib.query('ssp_conv_workspace_floats', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, base + 6413))
-                need = max(need, _lib.query('ssp_conv_workspace_floats', B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, base + 6413))
-            return need
-        max_ws = max(ws_need(cs) for cs in elig)
-        ws = torch.empty(max_ws, **f32)
-        # statistics scratch: the finest tiling any candidate uses (Winograd plans: groups of 16 tiles, counts behind the pairs)
-        stats = torch.empty(max(((cs.M + 15) // 16 + 16) * (cs.cout * 2 + 1) for cs in elig), **f32) if which == 'fwd' else None
-        gscratch = torch.zeros(max(cs.M * max(cs.inp.ld, cs.ldraw) for cs in elig), **f32) if which == 'dgrad' else None
-        verify = os.environ.get('SSP_TUNE_VERIFY', '1') != '0'
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(1234)
-
-        def best_of(launch, mn, key, extra=(), direct=None):
-            keep = True
-            if key in _TUNE_CACHE:       # the same launch shape was timed before (another plan, another model)
-                if not wino_tile(_TUNE_CACHE[key]) or _TUNE_CACHE[key] in extra:
-                    return _TUNE_CACHE[key]
-                keep = False             # a cached Winograd choice whose family is switched off in this process: time the
-                                         # other plans, leave the cache entry alone
-            best, best_t = 0, None
-            fams = {}                    # family (0 direct, 2 / 4 Winograd tile) -> (fastest code, ms)
-            # small-batch inference (valid.py runs B = 1): a few dozen tiles cannot stream the filters at HBM speed;
-            # deep K splits put every CU on the weight stream
-            deep = tuple(bm * 100 + ks * 10 + sl for bm in (64, 128) for ks in (4, 5, 6, 8, 9) for sl in (3, 4, 8)) \
-                if mn <= (1 << 21) else ()
-            # (direct: the direct-plan candidates of this launch when the standard list does not apply - a thin data
-            # gradient, Cin_dx <= 64, ignores plan codes: its heuristic plan alone is timed against the Winograd forms)
-            for code in (tuple(direct) if direct is not None else cands + (lat if mn <= (1 << 23) else ()) + deep) + tuple(extra):
-                if not wino_tile(code) and ((code // 10) % 10 > 1 or code >= 100000) and mn > (1 << 25):
-                    continue      # no split-K scratch for the biggest maps (dozens of waves: nothing to balance)
-                try:
-                    launch(code)
-                    ts = []
-                    for _ in range(2):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        launch(code)
-                        e1.record()
-                        e1.synchronize()
-                        ts.append(e0.elapsed_time(e1))
-                except _lib.SspError:
-                    continue
-                t = min(ts)
-                if wino_fused(code) and key[0] == 'dgrad':
-                    # ONE launch against the three of a through-HBM Winograd plan (transform, GEMM, finishing pass), and in the
-                    # step those run next to the filter-gradient stream: measured alone the two forms are within noise of each
-                    # other on the 104 x 104 layers (0.50-0.61 against 0.64 ms), in the step the on-chip form is the faster one
-                    # (three layers on it: 25.8 ms; one: 26.4 ms - a box whose timings fell the other way).  SSP_ONCHIP_PREFER
-                    # (default 0.85) credits it accordingly; 1 = the isolated timing decides.
-                    if t >= float(os.environ.get('SSP_ONCHIP_CREDIT_MS', '0.25')):      # (big launches only, as for the filter gradient)
-                        t *= float(os.environ.get('SSP_ONCHIP_PREFER', '0.85'))
-                if best_t is None or t < best_t * 0.985:     # prefer earlier (simpler) candidates on near-ties
-                    best, best_t = code, t
-                f_ = wino_tile(code)
-                if f_ not in fams or t < fams[f_][1] * 0.985:
-                    fams[f_] = (code, t)
-            if keep:
-                _TUNE_CACHE[key] = best
-                _TUNE_FAMILY[key] = fams
-            return best
-
-        def admitted(code, key, launch, out_of, operands, bn_of=None, prep=None, primary=True):
-            """verify-after-tune (see the docstring): code's result against plan 0's on seeded random operands.  A Winograd
-            plan is another ALGORITHM, not another summation order: its bar is 3e-5 of the output's range (measured ~1e-6)."""
-            if code == 0 or not verify or _TUNE_VERIFIED.get(key) == code or (key, code) in _TUNE_VERIFIED_ALSO:
-                return code
-            # Operands are the plan's own buffers (they hold no data yet: tuning runs before the first forward, and
-            # Plan.backward's fallback never tunes).  Only the columns a launch owns are randomised: the channel padding of
-            # a torch.zeros-allocated activation must stay zero for its consumers.
-            for t in operands:
-                (t[0].view(-1, t[1])[:, t[2]:t[2] + t[3]] if isinstance(t, tuple) else t).uniform_(-1.0, 1.0, generator=gen)
-            if prep is not None:
-                prep()                # operands changed: derived operands (Winograd-transformed filters) follow
-            bar = 3e-5 if wino_tile(code) else 1e-5
-            res = []
-            for c in (0, code):
-                launch(c)
-                r = [out_of().clone()]
-                if bn_of is not None:
-                    r += bn_of(c)
-                res.append(r)
-            ok = True
-            for a, b in zip(res[0], res[1]):
-                den = float(a.abs().max())
-                err = float((a - b).abs().max())
-                if not (err <= bar * max(den, 1e-30)):      # also false for NaN
-                    ok = False
-            if ok:
-                if primary:
-                    _TUNE_VERIFIED[key] = code
-                else:
-                    _TUNE_VERIFIED_ALSO.add((key, code))
-                return code
-            TUNE_REJECTED.append((key, code))
-            if primary:
-                _TUNE_CACHE[key] = 0
-            import warnings
-            warnings.warn("singleshotpose_amd: verify-after-tune refused plan %d for launch %s (result differs from the "
-                          "default plan's); the default plan runs" % (code, key))
-            return 0
-
-        for cs in elig:
-            if which == 'fwd' and (cs.cout > 64 or fused_ok(cs, which)):
-                # operand contents are irrelevant for timing: a channels-last-sized parameter stands in for itself
-                wop = cs.conv.weight if cs.cinp == cs.cin else self._wbuf(cs)
-                key = ('fwd', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, cs.inp.ld, cs.ldraw, bool(cs.bn), _tune_tag())
-
-                wc = wino_codes(cs, which, cs.M * cs.coutp <= (1 << 23))
-
-                def prep_f(tile, cs=cs, wop=wop):
-                    call('ssp_wino_filter_transform_t', wop.data_ptr(), self._wino_u(cs, tile).data_ptr(), cs.cout, cs.cinp,
-                         tile, st)
-
-                def launch(code, cs=cs, wop=wop):
-                    wt = self._wino_u(cs, wino_tile(code)) if wino_tile(code) else wop
-                    call('ssp_conv_fwd', cs.inp.ptr, wt.data_ptr(), cs.raw.data_ptr(), None,
-                         stats.data_ptr() if cs.bn else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
-                         cs.k, 0, code, ws.data_ptr(), max_ws, st)
-
-                def bn_of(code, cs=cs):
-                    # batch statistics from this plan's per-tile (mean, M2) partials: mean and 1/std per channel
-                    tm = _lib.query('ssp_conv_stats_tile_m', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
-                    nt = _lib.query('ssp_conv_stats_tiles', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
-                    tmp = torch.zeros(8, cs.coutp, **f32)
-                    tmp[0].fill_(1.0)
-                    tmp[3].fill_(1.0)
-                    call('ssp_bn_fwd_finalize', stats.data_ptr(), nt, tm, cs.M, cs.cout,
-                         tmp[0].data_ptr(), tmp[1].data_ptr(), tmp[2].data_ptr(), tmp[3].data_ptr(), BN_MOMENTUM,
-                         BN_EPS, tmp[4].data_ptr(), tmp[5].data_ptr(), tmp[6].data_ptr(), tmp[7].data_ptr(), st)
-                    return [tmp[4, :cs.cout].clone(), tmp[5, :cs.cout].clone()]
-
-                if wc and key not in _TUNE_CACHE:
-                    for t in sorted(set(wino_tile(c) for c in wc)):
-                        prep_f(t)
-                # (Cout <= 64 ignores direct plan codes - its heuristic plan alone is timed against the Winograd forms)
-                code = best_of(launch, cs.M * cs.coutp, key, wc, direct=None if cs.cout > 64 else (0,))
-                a = cs.inp
-                ops_ = [(a.t, a.ld, a.off % a.ld, cs.cinp)] + ([] if wop is cs.conv.weight else [wop])
-                cs.plan_fwd = admitted(code, key, launch, lambda cs=cs: cs.raw, ops_, bn_of if cs.bn else None,
-                                       (lambda code=code: prep_f(wino_tile(code))) if wino_tile(code) else None)
-                # The fastest code of every OTHER family that was timed (direct / F(2x2) / F(4x4)), verified the same way: what
-                # the error budget of the forward plans may fall back to (_apply_head_budget); a refused one is dropped.
-                cs.fwd_fams = {}
-                for f_, (c_, t_) in (_TUNE_FAMILY.get(key) or {}).items():
-                    if c_ == cs.plan_fwd:
-                        cs.fwd_fams[f_] = (c_, t_)
-                    elif c_ != code and admitted(c_, key, launch, lambda cs=cs: cs.raw, ops_, bn_of if cs.bn else None,
-                                                 (lambda c_=c_: prep_f(wino_tile(c_))) if wino_tile(c_) else None,
-                                                 primary=False) == c_:
-                        cs.fwd_fams[f_] = (c_, t_)
-                # a direct family whose tuned code was refused still has the library's heuristic plan (code 0, the reference of
-                # every verification): the error budget must always be able to fall back to a direct launch
-                fams_ = _TUNE_FAMILY.get(key) or {}
-                if 0 not in cs.fwd_fams and 0 in fams_:
-                    cs.fwd_fams[0] = (0, fams_[0][1])
-                # not chosen: the transformed-filter buffers go back to the allocator
-                cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
-            if which == 'dgrad' and not cs.first and cs.coutp % 16 == 0 and (cs.cin > 64 or wino_codes(cs, which)):
-                key = self._dgrad_key(cs)
-                wslice = self._dpack[cs.doff:cs.doff + cs.cinp * cs.k * cs.k * cs.coutp]
-
-                wc = wino_codes(cs, which)
-
-                def prep_d(tile, cs=cs):
-                    call('ssp_wino_filter_transform_t', _ptr(self._dpack, cs.doff), self._wino_ud(cs, tile).data_ptr(), cs.cin,
-                         cs.coutp, tile, st)
-
-                def launch(code, cs=cs):
-                    wt = self._wino_ud(cs, wino_tile(code)).data_ptr() if wino_tile(code) else _ptr(self._dpack, cs.doff)
-                    call('ssp_conv_dgrad', cs.raw.data_ptr(), wt, gscratch.data_ptr(), B, cs.H,
-                         cs.W, cs.coutp, cs.cin, cs.ldraw, cs.inp.ld, cs.k, 0, code, ws.data_ptr(), max_ws, st)
-
-                if wc and key not in _TUNE_CACHE:
-                    for t in sorted(set(wino_tile(c) for c in wc)):
-                        prep_d(t)
-                code = best_of(launch, cs.M * cs.cinp, key, wc, direct=None if cs.cin > 64 else (0,))
-                cs.plan_dgrad = admitted(code, key, launch, lambda cs=cs: gscratch[:cs.M * cs.inp.ld],
-                                         [(cs.raw, cs.ldraw, 0, cs.cout), wslice], None,
-                                         (lambda code=code: prep_d(wino_tile(code))) if wino_tile(code) else None)
-                cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
-        if self.conv_math['mode'] == 'bf16x3':
-            # bf16x3 mode, after (and apart from) the decisions above: the launch's direct fp32 code against the bf16x3 codes
-            # (tile rows 64 / 128 x the split depths the direct list tries at this grid size), timed the same way, near-ties
-            # to the fp32 code, verified against plan 0 at the direct family's 1e-5.  Keys of their own ('fwd-bf16x3' /
-            # 'dgrad-bf16x3'): nothing above reads them.  Plan._apply_conv_math / _conv_math_dgrad make the substitutions.
-            def timed(launch, code):
-                try:
-                    launch(code)
-                    ts = []
-                    for _ in range(2):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        launch(code)
-                        e1.record()
-                        e1.synchronize()
-                        ts.append(e0.elapsed_time(e1))
-                    return min(ts)
-                except _lib.SspError:
-                    return None
-
-            def x3_pick(cs, K, N, launch, xkey, fp32_code):
-                if xkey in _TUNE_CACHE:
-                    return _TUNE_CACHE[xkey]
-                mn = cs.M * _pad4(N)
-                splits = (1,) if mn > (1 << 25) else (1, 2, 3) + ((4, 5, 6, 8, 9) if mn <= (1 << 21) else ())
-                best, best_t = 0, timed(launch, fp32_code)
-                for bm in (128, 64):
-                    for ks in splits:
-                        code = BF16X3 + bm * 100 + ks * 10 + 3
-                        if not _lib.query('ssp_conv_bf16x3_fits', B, cs.H, cs.W, K, N, cs.k, code):
-                            continue
-                        t = timed(launch, code)
-                        if t is not None and (best_t is None or t < best_t * 0.985):
-                            best, best_t = code, t
-                _TUNE_CACHE[xkey] = best
-                return best
-
-            for cs in elig:
-                if cs.first:
-                    continue
-                if which == 'fwd' and _lib.query('ssp_conv_bf16x3_fits', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, BF16X3 + 12813):
-                    wop = cs.conv.weight if cs.cinp == cs.cin else self._wbuf(cs)
-                    xkey = ('fwd-bf16x3', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, cs.inp.ld, cs.ldraw, bool(cs.bn), _tune_tag())
-
-                    def launch(code, cs=cs, wop=wop):
-                        call('ssp_conv_fwd', cs.inp.ptr, wop.data_ptr(), cs.raw.data_ptr(), None,
-                             stats.data_ptr() if cs.bn else None, B, cs.H, cs.W, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw,
-                             cs.k, 0, code, ws.data_ptr(), max_ws, st)
-
-                    def bn_of(code, cs=cs):
-                        tm = _lib.query('ssp_conv_stats_tile_m', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
-                        nt = _lib.query('ssp_conv_stats_tiles', B, cs.H, cs.W, cs.cinp, cs.cout, cs.k, code)
-                        tmp = torch.zeros(8, cs.coutp, **f32)
-                        tmp[0].fill_(1.0)
-                        tmp[3].fill_(1.0)
-                        call('ssp_bn_fwd_finalize', stats.data_ptr(), nt, tm, cs.M, cs.cout,
-                             tmp[0].data_ptr(), tmp[1].data_ptr(), tmp[2].data_ptr(), tmp[3].data_ptr(), BN_MOMENTUM,
-                             BN_EPS, tmp[4].data_ptr(), tmp[5].data_ptr(), tmp[6].data_ptr(), tmp[7].data_ptr(), st)
-                        return [tmp[4, :cs.cout].clone(), tmp[5, :cs.cout].clone()]
-
-                    # the direct code the layer runs when it ends on one (now, or when the head budget moves it there)
-                    fp32_code = (cs.fwd_fams or {}).get(0, (0 if wino_tile(cs.plan_fwd) else cs.plan_fwd, None))[0]
-                    a = cs.inp
-                    ops_ = [(a.t, a.ld, a.off % a.ld, cs.cinp)] + ([] if wop is cs.conv.weight else [wop])
-                    cs.x3_fwd = admitted(x3_pick(cs, cs.cinp, cs.cout, launch, xkey, fp32_code), xkey, launch,
-                                         lambda cs=cs: cs.raw, ops_, bn_of if cs.bn else None)
-                if which == 'dgrad' and not wino_tile(cs.plan_dgrad) and _lib.query(
-                        'ssp_conv_bf16x3_fits', B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, BF16X3 + 12813):
-                    xkey = ('dgrad-bf16x3',) + self._dgrad_key(cs)[1:]
-                    wslice = self._dpack[cs.doff:cs.doff + cs.cinp * cs.k * cs.k * cs.coutp]
-
-                    def launch(code, cs=cs):
-                        call('ssp_conv_dgrad', cs.raw.data_ptr(), _ptr(self._dpack, cs.doff), gscratch.data_ptr(), B, cs.H,
-                             cs.W, cs.coutp, cs.cin, cs.ldraw, cs.inp.ld, cs.k, 0, code, ws.data_ptr(), max_ws, st)
-
-                    cs.x3_dgrad = admitted(x3_pick(cs, cs.coutp, cs.cin, launch, xkey, cs.plan_dgrad), xkey, launch,
-                                           lambda cs=cs: gscratch[:cs.M * cs.inp.ld], [(cs.raw, cs.ldraw, 0, cs.cout), wslice])
-        torch.cuda.synchronize()
-        if len(_TUNE_CACHE) != n_known:
-            _tune_cache_save()
-        # the timing / verification scratch (workspaces for the deepest candidate, gradient scratch, twin outputs) goes back
-        # to the driver: left in the caching allocator it sits reserved next to the plan's own buffers (multi-scale soak)
-        torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, training, need_grad=False, inline_repack=False, trainable=None, want_input=True):

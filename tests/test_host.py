@@ -416,6 +416,21 @@ def test_tune_cache_keys_carry_the_candidate_set(monkeypatch):
     assert len({both, only2, off}) == 3
 
 
+def test_committed_plan_set_carries_the_default_tag(monkeypatch, root_dir):
+    """Every key of cfg/bench_tune_cache.json that carries a candidate-set tag carries the one a default environment gives:
+    a tag that spelled a knob differently would leave the benchmark's committed plan set unread."""
+    import json
+    from singleshotpose_amd import engine
+    for k in ('SSP_WINOGRAD', 'SSP_WINO_TILES', 'SSP_WINO_MIN_CHANNELS', 'SSP_WINO4_MIN_CHANNELS', 'SSP_WINO_FUSED',
+              'SSP_WGRAD_FUSED_PREFER', 'SSP_ONCHIP_PREFER', 'SSP_ONCHIP_CREDIT_MS'):
+        monkeypatch.delenv(k, raising=False)
+    tag = engine._tune_tag()
+    with open(os.path.join(root_dir, 'cfg', 'bench_tune_cache.json')) as f:
+        keys = [json.loads(k.split('|', 1)[-1]) for k in json.load(f)]
+    tags = [x for k in keys for x in k if isinstance(x, str) and x[:1] == 'r' and x[1:2].isdigit() and x[2:3] == '-']
+    assert len(tags) == len(keys) and set(tags) == {tag}
+
+
 def test_error_budget_choice_on_the_measured_table():
     """engine.choose_under_budget on the table the MI355X measured for yolo-pose.cfg at 416 x 416, batch 64
     (profiles/r05_bench.json head_budget): head deviation of F(4x4) / F(2x2) against the direct code, launch times in ms."""
