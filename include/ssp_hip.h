@@ -117,7 +117,10 @@ int ssp_conv_dgrad(const float* dy, const float* wt, float* dx, int B, int H, in
  * i.e. what ssp_bn_act_bwd's reduce pass would re-read g and raw for; ssp_bn_act_bwd_partials finishes the block.
  * partial: partial_rows * Cin_dx * 2 floats.  A launch with ntile = ssp_conv_stats_tiles(...) <= partial_rows tiles stores row
  * `tile` plainly (deterministic); a launch with more tiles folds tile t into row t % partial_rows with fp32 atomic adds,
- * and the buffer must then be ZERO on entry (ssp_bn_act_bwd_partials with zero_after = 1 leaves it so).  Cin_dx % 4 == 0. */
+ * and the buffer must then be ZERO on entry (ssp_bn_act_bwd_partials with zero_after = 1 leaves it so).  Cin_dx % 4 == 0.
+ * partial_rows < 0 refuses the folding for THIS call: the buffer has -partial_rows rows, and a launch with more tiles than
+ * that is an error (nothing is launched, nothing written) instead of a run with atomics.  The same holds for
+ * ssp_conv_dgrad_adj_bnbwd. */
 int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
                          int lddy, int lddx, int R, int plan, float* workspace, int64_t workspace_floats,
                          const float* raw, int ldraw, const float* scale, const float* shift, const float* mean,
@@ -196,6 +199,45 @@ int ssp_conv_wgrad_wino_t(const float* dy, const float* x, float* dw, int B, int
 int64_t ssp_conv_wgrad_wino_workspace_floats(int B, int H, int W, int Cin, int Cout);
 int ssp_conv_wgrad_wino(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                         int ldx, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ---- ordered filter gradients (appended to ABI 5; csrc/wgrad_ordered.h): the same sums, bitwise reproducible ------------
+ * ssp_conv_wgrad, ssp_conv_s2_wgrad and a split ssp_conv_wgrad_wino_t launch add their per-pixel-range partial sums into
+ * the gradient with fp32 atomics, in the order the hardware retires them: two runs on the same operands differ in the last
+ * bits.  The entry points below run the SAME main loops (an epilogue argument of the same kernels) but every (filter tile,
+ * pixel range) workgroup stores its partial tile plainly into slab `range` of a caller-owned workspace
+ * [nsplit][Cout][R*R][Cin], and a finishing kernel adds the slabs of each element in the order 0 .. nsplit-1 (in float64,
+ * rounded once; flags bit 0 = in fp32) and performs the one dw += of the launch.  dw need NOT be zero: the launch
+ * accumulates onto it, exactly once per element.  Same operands, layouts and limits as the atomic entry points; stride =
+ * 1 (every route family of ssp_conv_wgrad_route) or 2 (H, W = the INPUT map, as ssp_conv_s2_wgrad).
+ *   split: the number of pixel ranges - an ARGUMENT, not process state (ssp_set_option is not consulted: the routes are
+ *     those of wgrad_variant 0): 0 = the library's choice, a pure host function of the shape built on a fixed model of the
+ *     chip (256 CUs, workgroups per CU from the kernel's LDS ring) instead of the occupancy the runtime reports, so it is
+ *     the same in every process; > 0 = that many ranges, CLAMPED to one staged chunk (16 pixels; 32 or 64 for thin tiles,
+ *     64 for the 4-channel kernel) per range, and - ranges are whole chunks - reduced to the count the rounded range
+ *     length gives (7 ranges asked of 338 pixels in chunks of 16 = 6 ranges of 64).  ssp_conv_wgrad_ordered_split returns
+ *     the count a launch with these arguments runs, ssp_conv_wgrad_ordered_workspace_floats = that count * Cout * R*R * Cin;
+ *     both are pure host functions (no GPU is touched) and return 0 where ssp_conv_wgrad_route returns 0 (a refused shape).
+ *   workspace: 16-byte aligned, at least the query's floats; every float of the first nsplit slabs is written, nothing
+ *     past them.  Two launches must not share a workspace concurrently.
+ * Results with different splits agree to fp32 rounding, not bit for bit: the split is part of what "the same launch" means. */
+int ssp_conv_wgrad_ordered_split(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int stride, int split);
+int64_t ssp_conv_wgrad_ordered_workspace_floats(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int stride,
+                                                int split);
+int ssp_conv_wgrad_ordered(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy, int ldx,
+                           int R, int stride, int split, int flags, float* workspace, int64_t workspace_floats, void* stream);
+/* The Winograd filter gradient (tiles 2 and 4; tile 12 adds with atomics on the chip and is refused) in the ordered form:
+ * the batched dU launch writes one transform-domain gradient [(tile+2)^2][Cout][Cin] per pixel (= tile row) range and
+ * the finishing kernel sums them in order before the back-transform G^T dU G.  split as above (ranges of 16 tile rows);
+ * workspace = ssp_conv_wgrad_wino_workspace_floats_t + (nsplit - 1) * (tile+2)^2 * Cout * Cin floats, laid out V | dM |
+ * dU slab 0 | ... | slab nsplit-1, so x == NULL / dy == NULL share V and dM as with ssp_conv_wgrad_wino_t.  0 = refused. */
+int ssp_conv_wgrad_wino_ordered_split(int B, int H, int W, int Cin, int Cout, int tile, int split);
+int64_t ssp_conv_wgrad_wino_ordered_workspace_floats(int B, int H, int W, int Cin, int Cout, int tile, int split);
+int ssp_conv_wgrad_wino_ordered(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
+                                int ldx, int tile, int split, float* workspace, int64_t workspace_floats, void* stream);
+/* ssp_conv_s2_dgrad with the tap split of small grids refused for THIS call: one thread per pixel on every grid, no atomics,
+ * the same bits from run to run (slower on grids under 512 workgroups: the longest workgroup contracts four taps). */
+int ssp_conv_s2_dgrad_ordered(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                              int lddx, int R, int accumulate, void* stream);
 
 /* ---- stride-2 convolution (appended to ABI 5; csrc/conv_strided.hip): nn.Conv2d(Cin, Cout, R, stride 2, padding R/2) at
  * darknet.py:156,160 with stride = 2, R = 1 or 3, exact fp32 on the matrix cores, any position of a net but the first

@@ -114,10 +114,18 @@ _SIGS = {
     "ssp_prof_nkinds": [],
     "ssp_prof_collect": [P, P, P],
     "ssp_conv_bf16x3_fits": [I, I, I, I, I, I, I],
+    "ssp_conv_wgrad_ordered_split": [I, I, I, I, I, I, I, I, I, I],
+    "ssp_conv_wgrad_ordered_workspace_floats": [I, I, I, I, I, I, I, I, I, I],
+    "ssp_conv_wgrad_ordered": [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, L, P],
+    "ssp_conv_wgrad_wino_ordered_split": [I, I, I, I, I, I, I],
+    "ssp_conv_wgrad_wino_ordered_workspace_floats": [I, I, I, I, I, I, I],
+    "ssp_conv_wgrad_wino_ordered": [P, P, P, I, I, I, I, I, I, I, I, I, P, L, P],
+    "ssp_conv_s2_dgrad_ordered": [P, P, P, I, I, I, I, I, I, I, I, I, P],
 }
 
 _RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_dgrad_adj_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',
-          'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles')
+          'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_conv_wgrad_ordered_workspace_floats',
+          'ssp_conv_wgrad_wino_ordered_workspace_floats', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles')
 
 PROF_KINDS = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_act", "layout", "region", "optim", "first_block_fwd",
               "first_block_bwd", "wino_fwd", "wino_dgrad", "wino_wgrad", "onchip_fwd", "onchip_dgrad", "onchip_wgrad")

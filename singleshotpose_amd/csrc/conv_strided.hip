@@ -23,6 +23,7 @@
 // The K loop is the register-staged pipeline of conv_igemm.hip (LDS ring of 3 slots, one barrier per chunk, branch-free
 // loads: out-of-map taps read a clamped address and are zeroed when they are stored to the LDS).
 #include "conv_igemm_common.h"
+#include "wgrad_ordered.h"
 
 struct S2Class {
   int py, px;          // data gradient: parity of the destination pixel (forward: 0, 0)
@@ -382,7 +383,7 @@ int ssp_conv_s2_fwd_launch(const float* in, const float* wt, float* out, const f
 }
 
 int ssp_conv_s2_dgrad_launch(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
-                             int lddy, int lddx, int R, int accumulate, hipStream_t stream) {
+                             int lddy, int lddx, int R, int accumulate, hipStream_t stream, int no_tap_split) {
   S2_CHECK_COMMON("conv_s2_dgrad", B, H, W, R);
   SSP_CHECK_ARG(Cout_dy % 4 == 0 && Cout_dy > 0, "conv_s2_dgrad: Cout_dy must be a positive multiple of 4 (got %d)", Cout_dy);
   SSP_CHECK_ARG(lddy % 4 == 0 && lddy >= Cout_dy, "conv_s2_dgrad: lddy must be a multiple of 4 and >= Cout_dy");
@@ -430,7 +431,7 @@ int ssp_conv_s2_dgrad_launch(const float* dy, const float* wt, float* dx, int B,
     const S2Tile t = s2_tile(Ms, a.ncls, Cin_dx);
     int64_t wgs = 0;
     for (int k = 0; k < a.ncls; ++k) wgs += (Ms[k] + t.bm - 1) / t.bm;
-    split = wgs * ssp_cdiv(Cin_dx, t.bn) < 512;
+    split = wgs * ssp_cdiv(Cin_dx, t.bn) < 512 && !no_tap_split;      // (ordered form: one thread per pixel on every grid)
   }
   if (split) {
     S2Args b = a;
@@ -464,6 +465,7 @@ struct S2WgradArgs {
   int H, W, Ho, Wo, Cin, Cout, lddy, ldx, R, M;
   int ntile_co, ntile_ci, nsplit, chunk_m;
   SspFastDiv divW, divH;
+  int64_t slab_floats;      // ordered form (wgrad_ordered.h): > 0 = dw is the workspace [nsplit][slab_floats], plain stores
 };
 
 // conv_wgrad.hip's register-staged kernel (GEMM per tap: rows = cout, cols = cin, reduction = output pixels split across
@@ -630,6 +632,10 @@ __global__ void __launch_bounds__(256, 2) conv_s2_wgrad_kernel(S2WgradArgs p) {
     slot = slot1;
   }
 
+  if (p.slab_floats > 0) {      // ordered form: plain stores into this pixel range's slab
+    ssp_wgrad_ordered_store<BMO, BNI, WM, WN, WK>(acc, smem, p.dw + (int64_t)split * p.slab_floats, p.Cin, p.Cout, taps, tap, co0, ci0);
+    return;
+  }
   // (WK > 1: the k-groups of waves hold partial sums of the same filter tile; every group adds its own)
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -656,6 +662,12 @@ static int s2_launch_wgrad(S2WgradArgs a, hipStream_t stream) {
   static SspKernelCache cache;   // per instantiation, per device
   int slots = 0;                 // workgroups resident on the whole chip (occupancy x CUs)
   if (int rc = ssp_kernel_prepare((const void*)kern, lds_bytes, 256, &cache, &slots, "conv_s2_wgrad")) return rc;
+  if (a.slab_floats > 0) {       // ordered form: the pixel ranges were fixed on the host (ssp_wgrad_ordered_plan)
+    SSP_CHECK_ARG(a.chunk_m % RA == 0 && a.nsplit >= 1 && tiles * a.nsplit < (1ll << 31), "conv_s2_wgrad (ordered): bad pixel ranges");
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.nsplit)), dim3(256), lds_bytes, stream, a);
+    SSP_CHECK_LAUNCH("conv_s2_wgrad(ordered)");
+    return SSP_OK;
+  }
   // pixel split as conv_wgrad.hip: a grid of 2..5 whole resident waves of workgroups, >= 8 staged chunks per workgroup
   const int64_t max_split = (a.M + RA * 8 - 1) / (RA * 8);
   int64_t lo = (2 * (int64_t)slots + tiles - 1) / tiles, hi = (5 * (int64_t)slots) / tiles;
@@ -681,8 +693,8 @@ static int s2_launch_wgrad(S2WgradArgs a, hipStream_t stream) {
   return SSP_OK;
 }
 
-int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
-                             int ldx, int R, hipStream_t stream) {
+static int s2_wgrad_launch_impl(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
+                                int ldx, int R, int nsplit, int chunk_m, int64_t slab_floats, hipStream_t stream) {
   S2_CHECK_COMMON("conv_s2_wgrad", B, H, W, R);
   SSP_CHECK_ARG(Cin % 4 == 0 && Cin > 0, "conv_s2_wgrad: Cin must be a positive multiple of 4 (got %d)", Cin);
   SSP_CHECK_ARG(ldx % 4 == 0 && ldx >= Cin, "conv_s2_wgrad: ldx must be a multiple of 4 and >= Cin");
@@ -694,8 +706,8 @@ int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, 
   a.H = H; a.W = W; a.Ho = s2_out(H, R); a.Wo = s2_out(W, R);
   a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = B * a.Ho * a.Wo;
   a.divW = ssp_fastdiv((unsigned)a.Wo); a.divH = ssp_fastdiv((unsigned)a.Ho);
-  a.ntile_co = a.ntile_ci = a.nsplit = a.chunk_m = 0;
-  SspProfScope prof(SSP_PROF_CONV_WGRAD, stream, 2.0 * (double)a.M * Cout * (double)(R * R * Cin));
+  a.ntile_co = a.ntile_ci = 0;
+  a.nsplit = nsplit; a.chunk_m = chunk_m; a.slab_floats = slab_floats;
   const int bmo = Cout > 64 ? 128 : (Cout > 32 ? 64 : 32), bni = Cin > 64 ? 128 : (Cin > 32 ? 64 : 32);
   switch (bmo * 1000 + bni) {
     case 128128: return s2_launch_wgrad<128, 128, 2, 2, 1>(a, stream);
@@ -708,4 +720,14 @@ int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, 
     case 32064: return s2_launch_wgrad<32, 64, 1, 2, 2>(a, stream);
     default: return s2_launch_wgrad<32, 32, 1, 1, 4>(a, stream);
   }
+}
+
+int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
+                             int ldx, int R, hipStream_t stream) {
+  SspProfScope prof(SSP_PROF_CONV_WGRAD, stream, 2.0 * (double)B * s2_out(H, R) * s2_out(W, R) * Cout * (double)(R * R * Cin));
+  return s2_wgrad_launch_impl(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, 0, 0, 0, stream);
+}
+int ssp_conv_s2_wgrad_ordered_launch(const float* dy, const float* x, float* ws, int B, int H, int W, int Cin, int Cout, int lddy,
+                                     int ldx, int R, const SspWgradOrderedPlan& pl, hipStream_t stream) {
+  return s2_wgrad_launch_impl(dy, x, ws, B, H, W, Cin, Cout, lddy, ldx, R, pl.nsplit, pl.chunk_m, pl.slab_floats, stream);
 }

@@ -13,7 +13,10 @@
 // The pixel reduction is split across workgroups (grid.x = tiles * taps * nsplit) and - for
 // thin layers - across the waves of a workgroup (WK); partial tiles are summed into dW with
 // hardware fp32 atomics, so the caller zeroes dW first.
+#include <type_traits>
+
 #include "conv_wino.h"
+#include "wgrad_ordered.h"
 
 struct WgradArgs {
   const float* dy;
@@ -21,6 +24,9 @@ struct WgradArgs {
   float* dw;
   int H, W, Cin, Cout, lddy, ldx, R, M;
   int ntile_co, ntile_ci, nsplit, chunk_m;
+  // ordered form (wgrad_ordered.h): slab_floats > 0 = dw is the workspace [nsplit][slab_floats]; pixel range `split` stores
+  // its partial tile plainly into slab `split` instead of adding it to the gradient with atomics
+  int64_t slab_floats;
 };
 
 // Pipeline: as conv_igemm.hip - LDS ring of 3 slots, one barrier per staged chunk of RA pixel rows; the registers hold
@@ -184,6 +190,10 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs p) {
     slot = slot1;
   }
 
+  if (p.slab_floats > 0) {      // ordered form: plain stores into this pixel range's slab
+    ssp_wgrad_ordered_store<BMO, BNI, WM, WN, WK>(acc, smem, p.dw + (int64_t)split * p.slab_floats, p.Cin, p.Cout, taps, tap, co0, ci0);
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -309,7 +319,8 @@ __global__ void __launch_bounds__(256) conv_wgrad_c4_kernel(WgradArgs p) {
     int co = e / 36, col = e % 36;
     float v = red[(0 * CO + co) * NCOL + col] + red[(1 * CO + co) * NCOL + col] + red[(2 * CO + co) * NCOL + col] +
               red[(3 * CO + co) * NCOL + col];
-    atomicAdd(p.dw + co * 36 + col, v);   // dw[co][tap][ci], Cin = 4
+    if (p.slab_floats > 0) p.dw[(int64_t)blockIdx.x * p.slab_floats + co * 36 + col] = v;      // ordered form: slab of this range
+    else atomicAdd(p.dw + co * 36 + col, v);   // dw[co][tap][ci], Cin = 4
   }
 }
 
@@ -324,6 +335,12 @@ static int launch_wgrad(WgradArgs a, hipStream_t stream) {
   static SspKernelCache cache;   // per instantiation, per device
   int slots = 0;                 // workgroups resident on the whole chip (occupancy x CUs)
   if (int rc = ssp_kernel_prepare((const void*)kern, lds_bytes, 256, &cache, &slots, "conv_wgrad")) return rc;
+  if (a.slab_floats > 0) {       // ordered form: the pixel ranges were fixed on the host (ssp_wgrad_ordered_plan)
+    SSP_CHECK_ARG(a.chunk_m % RA == 0 && a.nsplit >= 1 && tiles * a.nsplit < (1ll << 31), "conv_wgrad (ordered): bad pixel ranges");
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.nsplit)), dim3(256), lds_bytes, stream, a);
+    SSP_CHECK_LAUNCH("conv_wgrad(ordered)");
+    return SSP_OK;
+  }
   // Split the pixel reduction so that the grid is (close to) a whole number of resident waves of workgroups - a
   // 2.25-wave grid runs as long as a 3-wave one - with 2..5 waves in total and >= 8 staged chunks per workgroup.
   const int64_t max_split = (a.M + RA * 8 - 1) / (RA * 8);
@@ -365,6 +382,7 @@ int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int
   WgradArgs a;
   a.dy = dy; a.x = x; a.dw = dw;
   a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = B * H * W;
+  a.slab_floats = 0;
   SspProfScope prof(SSP_PROF_CONV_WGRAD, stream, 2.0 * (double)a.M * Cout * (double)(R * R * Cin));
   // one host function picks the instantiation (ssp_wgrad_route, conv_wgrad_dma.hip); the pixel split stays with the launchers
   const int route = ssp_wgrad_route(B, H, W, Cin, Cout, lddy, ldx, R, 0, ssp_option(SSP_OPT_WGRAD_VARIANT));
@@ -399,6 +417,150 @@ int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int
   return SSP_ERR_ARG;
 }
 
+// ---- ordered (bitwise-reproducible) form: wgrad_ordered.h ------------------------------------------------------------------
+// The pixel ranges of an ordered launch: a pure host function of the shape.  The atomic launchers size their split by the
+// occupancy the runtime reports for the kernel (ssp_kernel_prepare) - a number that may differ between processes, compute
+// partitions and library builds - so this rule uses a fixed model of the chip instead: 256 CUs, workgroups per CU from the
+// instantiation's LDS ring alone (160 KiB per CU, at most four).  The rule itself is launch_wgrad_dma's: the smallest
+// split that fills >= 93 % of whole resident waves of workgroups, one wave to five, >= 8 staged chunks per range.
+static int ordered_wk(int bmo, int bni) { return (bmo == 32 && bni == 32) ? 4 : ((bmo == 64 && bni == 32) || (bmo == 32 && bni == 64)) ? 2 : 1; }
+
+// M pixels in chunks of `ra`, `tiles` workgroups per pixel range, `lds_bytes` of LDS per workgroup; fixed > 0: that many
+// ranges when the caller forces none (the 4-channel kernel: ~8 workgroups per CU, as its atomic form).  false: refused.
+static bool ordered_ranges(int64_t M, int ra, int64_t tiles, int lds_bytes, int fixed, int split, int* nsplit_out, int* chunk_out) {
+  const int64_t max_forced = (M + ra - 1) / ra;      // a range holds at least one staged chunk
+  int64_t nsplit;
+  if (split > 0) {
+    nsplit = split < max_forced ? split : max_forced;
+  } else if (fixed > 0) {
+    nsplit = fixed < max_forced ? fixed : max_forced;
+  } else {
+    int per_cu = (160 * 1024) / lds_bytes;
+    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+    const int64_t slots = 256 * (int64_t)per_cu;
+    const int64_t max_split = (M + ra * 8 - 1) / (ra * 8);
+    int64_t lo = (slots + tiles - 1) / tiles, hi = (5 * slots) / tiles;
+    if (tiles >= (int64_t)(0.93 * slots)) lo = 1;
+    if (lo < 1) lo = 1;
+    if (hi < lo) hi = lo;
+    if (lo > max_split) lo = max_split;
+    if (hi > max_split) hi = max_split;
+    nsplit = lo;
+    double best = -1.0;
+    for (int64_t sp = lo; sp <= hi; ++sp) {
+      const double eff = ((double)(tiles * sp) / slots) / (double)((tiles * sp + slots - 1) / slots);
+      if (eff > best + 1e-3) { best = eff; nsplit = sp; }
+      if (eff >= 0.93) break;
+    }
+  }
+  int64_t chunk = (M + nsplit - 1) / nsplit;
+  chunk = (chunk + ra - 1) / ra * ra;
+  nsplit = (M + chunk - 1) / chunk;
+  if (tiles * nsplit >= (1ll << 31) || nsplit >= (1ll << 20)) return false;
+  *nsplit_out = (int)nsplit;
+  *chunk_out = (int)chunk;
+  return true;
+}
+
+SspWgradOrderedPlan ssp_wgrad_ordered_plan(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int stride, int split) {
+  SspWgradOrderedPlan pl = {0, 0, 0, 0, 0, 0};
+  if (split < 0) return pl;
+  int route = 0;
+  int64_t M = 0;
+  if (stride == 1) {
+    // (variant 0: the product's routes - the experiment knob of ssp_set_option is process state and stays out of this path)
+    route = ssp_wgrad_route(B, H, W, Cin, Cout, lddy, ldx, R, 0, 0);
+    M = (int64_t)B * H * W;
+  } else if (stride == 2) {
+    if (!(R == 1 || R == 3) || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (int64_t)B * H * W >= (1ll << 31)) return pl;
+    if (Cin <= 0 || Cin % 4 != 0 || ldx % 4 != 0 || ldx < Cin || lddy % 4 != 0 || lddy < Cout) return pl;
+    const int Ho = (H + 2 * (R / 2) - R) / 2 + 1, Wo = (W + 2 * (R / 2) - R) / 2 + 1;
+    M = (int64_t)B * Ho * Wo;
+    const int bmo = Cout > 64 ? 128 : (Cout > 32 ? 64 : 32), bni = Cin > 64 ? 128 : (Cin > 32 ? 64 : 32);
+    route = ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, bmo, bni);
+  }
+  if (route == 0 || M <= 0) return pl;
+  const int family = route / 100000000, nslot = (route / 10000000) % 10, flags = (route / 1000000) % 10;
+  const int bmo = (route / 1000) % 1000, bni = route % 1000, taps = R * R;
+  int ra, lds_bytes;
+  int64_t tiles;
+  if (family == SSP_WGRAD_C4) {
+    ra = 64; lds_bytes = 0; tiles = 1;
+  } else if (family == SSP_WGRAD_LDS) {
+    const int fold = (flags & 1) ? bni / Cin : 1;
+    ra = 16; lds_bytes = nslot * 16 * (bmo + bni) * 4;
+    tiles = (int64_t)ssp_cdiv(Cout, bmo) * ssp_cdiv(Cin, bni) * ssp_cdiv(taps, fold);
+  } else {
+    ra = 16 * ordered_wk(bmo, bni); lds_bytes = 3 * ra * (bmo + bni) * 4;
+    tiles = (int64_t)ssp_cdiv(Cout, bmo) * ssp_cdiv(Cin, bni) * taps;
+  }
+  int nsplit = 0, chunk = 0;
+  if (!ordered_ranges(M, ra, tiles, lds_bytes, family == SSP_WGRAD_C4 ? 2048 : 0, split, &nsplit, &chunk)) return pl;
+  pl.route = route; pl.ra = ra; pl.nsplit = nsplit; pl.chunk_m = chunk; pl.M = M;
+  pl.slab_floats = (int64_t)Cout * taps * Cin;
+  return pl;
+}
+
+// dw[e] += ws[0][e] + ws[1][e] + ... + ws[nsplit-1][e]: one thread per four elements, the slabs in index order.  F64: the sum
+// of the slabs is carried in float64 and rounded once (DESIGN.md section 3d has the measured error of both forms).
+template <bool F64>
+__global__ void __launch_bounds__(256) wgrad_ordered_finish_kernel(const float* __restrict__ ws, float* dw, int64_t n, int nsplit) {
+  using T = typename std::conditional<F64, double, float>::type;
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (i + 4 <= n) {
+    T s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    for (int k = 0; k < nsplit; ++k) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(ws + (int64_t)k * n + i);
+      s0 += (T)v[0]; s1 += (T)v[1]; s2 += (T)v[2]; s3 += (T)v[3];
+    }
+    dw[i] += (float)s0; dw[i + 1] += (float)s1; dw[i + 2] += (float)s2; dw[i + 3] += (float)s3;
+  } else {
+    for (int64_t e = i; e < n; ++e) {
+      T s = 0;
+      for (int k = 0; k < nsplit; ++k) s += (T)ws[(int64_t)k * n + e];
+      dw[e] += (float)s;
+    }
+  }
+}
+int ssp_wgrad_ordered_finish_launch(const float* ws, float* dw, int64_t n, int nsplit, int fp32_sum, hipStream_t stream) {
+  SSP_CHECK_ARG(n > 0 && n % 4 == 0 && nsplit >= 1, "wgrad (ordered) finish: bad size");
+  const unsigned grid = (unsigned)((n / 4 + 255) / 256);
+  if (fp32_sum) hipLaunchKernelGGL(wgrad_ordered_finish_kernel<false>, dim3(grid), dim3(256), 0, stream, ws, dw, n, nsplit);
+  else hipLaunchKernelGGL(wgrad_ordered_finish_kernel<true>, dim3(grid), dim3(256), 0, stream, ws, dw, n, nsplit);
+  SSP_CHECK_LAUNCH("wgrad_ordered_finish");
+  return SSP_OK;
+}
+
+int ssp_conv_wgrad_ordered_s1_launch(const float* dy, const float* x, float* ws, int B, int H, int W, int Cin, int Cout, int lddy,
+                                     int ldx, int R, const SspWgradOrderedPlan& pl, hipStream_t stream) {
+  if (pl.route / 100000000 == SSP_WGRAD_LDS)
+    return ssp_conv_wgrad_dma_ordered_launch(dy, x, ws, B, H, W, Cin, Cout, lddy, ldx, R, pl.route, pl.nsplit, pl.chunk_m,
+                                             pl.slab_floats, 0, 0, 0, 0, stream);
+  WgradArgs a;
+  a.dy = dy; a.x = x; a.dw = ws;
+  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = (int)pl.M;
+  a.nsplit = pl.nsplit; a.chunk_m = pl.chunk_m; a.slab_floats = pl.slab_floats;
+  a.ntile_co = a.ntile_ci = 0;
+  switch (pl.route) {
+    case ssp_wgrad_code(SSP_WGRAD_C4, 2, false, false, 32, 4):
+      hipLaunchKernelGGL(conv_wgrad_c4_kernel, dim3(a.nsplit), dim3(256), 0, stream, a);
+      SSP_CHECK_LAUNCH("conv_wgrad_c4(ordered)");
+      return SSP_OK;
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 128): return launch_wgrad<128, 128, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 64): return launch_wgrad<128, 64, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 128, 32): return launch_wgrad<128, 32, 4, 1, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 128): return launch_wgrad<64, 128, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 64): return launch_wgrad<64, 64, 2, 2, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 64, 32): return launch_wgrad<64, 32, 2, 1, 2>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 128): return launch_wgrad<32, 128, 1, 4, 1>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 64): return launch_wgrad<32, 64, 1, 2, 2>(a, stream);
+    case ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, 32, 32): return launch_wgrad<32, 32, 1, 1, 4>(a, stream);
+  }
+  ssp_set_error("wgrad (ordered): no instantiation for route %d", pl.route);
+  return SSP_ERR_ARG;
+}
+
 
 // Filter gradient of a 3x3 layer in the Winograd domain (conv_wino.hip): transform the input (B^T d B) and the output
 // gradient (A dY A^T) into P = (tile + 2)^2 planes each, contract the planes pairwise over the tiles in ONE batched launch
@@ -407,6 +569,32 @@ int ssp_conv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int
 // Winograd forward launch of the same tile size puts it (workspace head), so a caller that hands both launches the same
 // buffer transforms the layer input once per step.  dU needs no clearing by the caller: an un-split batched launch writes
 // it with plain stores, a split one zeroes it first.
+int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile);
+// The batched dU launch of an ordered Winograd filter gradient: P problems of T pixel rows on the LDS-direct kernel; its
+// pixel ranges by the same host rule as a direct launch.  false: tile / shape refused.
+static bool wino_ordered_ranges(int B, int H, int W, int Cin, int Cout, int tile, int split, int* route, int* nsplit, int* chunk) {
+  if ((tile != 2 && tile != 4) || split < 0 || B <= 0 || H <= 0 || W <= 0) return false;
+  if (Cin % 16 != 0 || Cout % 16 != 0 || Cin < 64 || Cout < 64) return false;
+  const int64_t T = ssp_wino_tiles(B, H, W, tile);
+  const int P = ssp_wino_planes(tile);
+  if (T < 16 || T >= (1ll << 31)) return false;
+  *route = ssp_wgrad_route(1, 1, (int)T, Cin, Cout, Cout, Cin, 1, P, 0);
+  if (*route / 100000000 != SSP_WGRAD_LDS) return false;
+  const int nslot = (*route / 10000000) % 10, bmo = (*route / 1000) % 1000, bni = *route % 1000;
+  const int64_t tiles = (int64_t)ssp_cdiv(Cout, bmo) * ssp_cdiv(Cin, bni) * P;
+  return ordered_ranges(T, 16, tiles, nslot * 16 * (bmo + bni) * 4, 0, split, nsplit, chunk);
+}
+int ssp_wino_wgrad_ordered_split(int B, int H, int W, int Cin, int Cout, int tile, int split) {
+  int route = 0, nsplit = 0, chunk = 0;
+  return wino_ordered_ranges(B, H, W, Cin, Cout, tile, split, &route, &nsplit, &chunk) ? nsplit : 0;
+}
+// V | dM | dU slab 0 | ... | dU slab nsplit-1: the un-ordered layout grown by the extra slabs
+int64_t ssp_conv_wgrad_wino_ordered_ws_floats(int B, int H, int W, int Cin, int Cout, int tile, int split) {
+  const int ns = ssp_wino_wgrad_ordered_split(B, H, W, Cin, Cout, tile, split);
+  if (ns <= 0) return 0;
+  return ssp_conv_wgrad_wino_ws_floats(B, H, W, Cin, Cout, tile) + (int64_t)(ns - 1) * ssp_wino_planes(tile) * Cin * Cout;
+}
+
 int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile) {
   if (tile == SSP_WINO_WGRAD_FUSED) return ssp_wino_wgrad_fused_ws_floats(Cin, Cout);      // dU alone: V and dM stay on the chip
   if (tile != 2 && tile != 4) return 0;
@@ -414,7 +602,10 @@ int64_t ssp_conv_wgrad_wino_ws_floats(int B, int H, int W, int Cin, int Cout, in
   return ssp_wino_planes(tile) * (T * ((int64_t)Cin + Cout) + (int64_t)Cin * Cout);
 }
 int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
-                               int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream) {
+                               int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream, int ordered_split) {
+  // ordered_split >= 0: the ordered form (0 = the library's split): per-range dU slabs, summed in order by the finishing kernel
+  if (ordered_split >= 0)
+    SSP_CHECK_ARG(tile == 2 || tile == 4, "wgrad (Winograd, ordered): tile must be 2 or 4 (the on-chip form adds with atomics)");
   if (tile == SSP_WINO_WGRAD_FUSED) {
     SSP_CHECK_ARG(dy != nullptr, "wgrad (Winograd, both transforms on the chip): dy must be given (no dM in memory to share)");
     return ssp_wino_wgrad_fused_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, ws, ws_floats, stream);
@@ -426,9 +617,11 @@ int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B
   const int64_t T = ssp_wino_tiles(B, H, W, tile);
   const int P = ssp_wino_planes(tile);
   SSP_CHECK_ARG(T >= 16 && T < (1ll << 31), "wgrad (Winograd): tile count out of range (>= 16 tiles)");
-  SSP_CHECK_ARG(ws != nullptr && ws_floats >= ssp_conv_wgrad_wino_ws_floats(B, H, W, Cin, Cout, tile),
-                "wgrad (Winograd): needs a workspace of %lld floats (ssp_conv_wgrad_wino_workspace_floats)",
-                (long long)ssp_conv_wgrad_wino_ws_floats(B, H, W, Cin, Cout, tile));
+  const int64_t need = ordered_split >= 0 ? ssp_conv_wgrad_wino_ordered_ws_floats(B, H, W, Cin, Cout, tile, ordered_split)
+                                          : ssp_conv_wgrad_wino_ws_floats(B, H, W, Cin, Cout, tile);
+  SSP_CHECK_ARG(need > 0, "wgrad (Winograd, ordered): shape declined by the LDS-direct filter-gradient kernel");
+  SSP_CHECK_ARG(ws != nullptr && ws_floats >= need,
+                "wgrad (Winograd): needs a workspace of %lld floats (ssp_conv_wgrad_wino_workspace_floats)", (long long)need);
   SspProfScope prof(SSP_PROF_CONV_WGRAD, stream, 2.0 * (double)B * H * W * Cout * 9.0 * Cin);      // algorithmic (direct) FLOPs
   float* V = ws;
   float* dM = V + P * T * Cin;
@@ -442,6 +635,14 @@ int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B
   // gradient (ssp_conv_dgrad_adj), which contracts the same planes
   if (dy != nullptr)
     if (int rc = ssp_wino_outgrad_launch(dy, lddy, dM, B, H, W, Cout, tile, stream)) return rc;
+  if (ordered_split >= 0) {
+    int route = 0, nsplit = 0, chunk = 0;
+    SSP_CHECK_ARG(wino_ordered_ranges(B, H, W, Cin, Cout, tile, ordered_split, &route, &nsplit, &chunk), "wgrad (Winograd, ordered): shape declined");
+    const int64_t slab = (int64_t)P * Cout * Cin;
+    if (int rc = ssp_conv_wgrad_dma_ordered_launch(dM, V, dU, 1, 1, (int)T, Cin, Cout, Cout, Cin, 1, route, nsplit, chunk, slab, P,
+                                                   T * Cout, T * Cin, (int64_t)Cout * Cin, stream)) return rc;
+    return ssp_wino_wgrad_finish_launch(dU, dw, Cout, Cin, tile, stream, nsplit, slab);
+  }
   const int r = ssp_conv_wgrad_dma_try(dM, V, dU, 1, 1, (int)T, Cin, Cout, Cout, Cin, 1, stream, P, T * Cout, T * Cin,
                                        (int64_t)Cout * Cin, 1);
   if (r < 0) return r;

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "ssp_common.h"
+#include "wgrad_ordered.h"
 
 struct WgradArgs {
   const float* dy;
@@ -35,6 +36,10 @@ struct WgradArgs {
   int store;
   void* zero_ptr;
   size_t zero_bytes;
+  // ordered form (wgrad_ordered.h): slab_floats > 0 = pixel range `split` of every problem stores its partial tiles (store =
+  // 1) into slab `split` of dw = a workspace [nsplit][slab_floats]; nsplit and chunk_m come from the caller (a pure host
+  // function of the shape), the launcher neither asks the runtime for the occupancy nor reorders the workgroups
+  int64_t slab_floats;
 };
 
 #define SSP_OOB 0x80000000u
@@ -129,7 +134,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_dma_kernel(WgradArgs p) {
   const int64_t bz = (p.batch > 1) ? (int64_t)blockIdx.y : 0;   // batched launch: problem index (scalar)
   const float* const dy_b = p.dy + bz * p.batch_dy;
   const float* const x_b = p.x + bz * p.batch_x;
-  float* const dw_b = p.dw + bz * p.batch_dw;
+  float* const dw_b = p.dw + bz * p.batch_dw + (int64_t)split * p.slab_floats;
 
   // ---- loader lanes: piece g (1 KiB) of a tile = bytes [g*1024, g*1024+1024) of the row-major [16][C] image ----
   // A 1-KiB piece of the X tile covers RP consecutive pixel rows (BNI = 128: 2 rows of 512 B, BNI = 64: 4 rows of
@@ -406,6 +411,15 @@ static int launch_wgrad_dma(WgradArgs a, hipStream_t stream) {
   static SspKernelCache cache;   // per instantiation, per device
   int slots = 0;
   if (int rc = ssp_kernel_prepare((const void*)kern, lds_bytes, 256, &cache, &slots, "conv_wgrad_dma")) return rc;
+  if (a.slab_floats > 0) {       // ordered form: fixed pixel ranges, plain workgroup order, plain stores into the slabs
+    SSP_CHECK_ARG(a.chunk_m % RA == 0 && a.nsplit >= 1 && (tiles / nbatch) * a.nsplit < (1ll << 31), "conv_wgrad_dma (ordered): bad pixel ranges");
+    a.no_store = 0;
+    a.xcd_order = 0;
+    a.store = 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((tiles / nbatch) * a.nsplit), nbatch), dim3(256), lds_bytes, stream, a);
+    SSP_CHECK_LAUNCH("conv_wgrad_dma(ordered)");
+    return SSP_OK;
+  }
   // Split over pixels.  Every workgroup ends with BMO x BNI atomics onto its filter tile, and all workgroups of a tile
   // hit the same lines: on the layers with few tiles (layers 4-16: 9-72 tiles) the atomic traffic is 5-12 % of the
   // launch, so the split is the SMALLEST one that fills whole resident waves of workgroups (>= 93 % of the last wave),
@@ -548,6 +562,8 @@ int ssp_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, i
   return ssp_wgrad_code(SSP_WGRAD_REG, 3, false, false, bo, bi);
 }
 
+static int wgrad_dma_dispatch(int route, const WgradArgs& a, hipStream_t stream);
+
 // returns 1 when the shape is handled here (launched), 0 when the caller should use conv_wgrad.hip, < 0 on error
 int ssp_conv_wgrad_dma_try(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                            int ldx, int R, hipStream_t stream, int batch, int64_t batch_dy, int64_t batch_x,
@@ -562,10 +578,16 @@ int ssp_conv_wgrad_dma_try(const float* dy, const float* x, float* dw, int B, in
   a.store = 0;
   a.zero_ptr = nullptr;
   a.zero_bytes = 0;
+  a.slab_floats = 0;
   if (overwrite) {      // dw = result (not +=): the launcher stores when it does not split, zeroes first when it does
     a.zero_ptr = dw;
     a.zero_bytes = (size_t)(batch > 1 ? batch : 1) * (size_t)(batch > 1 ? batch_dw : (int64_t)Cout * R * R * Cin) * 4;
   }
+  const int rc = wgrad_dma_dispatch(route, a, stream);
+  return rc == SSP_OK ? 1 : rc;
+}
+
+static int wgrad_dma_dispatch(int route, const WgradArgs& a, hipStream_t stream) {
   int rc;
   switch (route) {
     case ssp_wgrad_code(SSP_WGRAD_LDS, 4, true, false, 128, 64): rc = launch_wgrad_dma<128, 64, 4, true>(a, stream); break;
@@ -581,5 +603,23 @@ int ssp_conv_wgrad_dma_try(const float* dy, const float* x, float* dw, int B, in
       ssp_set_error("conv_wgrad_dma: no instantiation for route %d", route);
       return SSP_ERR_ARG;
   }
-  return rc == SSP_OK ? 1 : rc;
+  return rc;
+}
+
+// The ordered form of a launch of route `route` (an LDS-direct code): pixel range s of problem b stores its partial tiles into
+// ws + s * slab_floats + b * batch_dw.  One problem: slab_floats = Cout * R*R * Cin; a batched launch (the planes of a
+// Winograd filter gradient): slab_floats = batch * batch_dw, every slab a whole transform-domain gradient.
+int ssp_conv_wgrad_dma_ordered_launch(const float* dy, const float* x, float* ws, int B, int H, int W, int Cin, int Cout, int lddy,
+                                      int ldx, int R, int route, int nsplit, int chunk_m, int64_t slab_floats, int batch,
+                                      int64_t batch_dy, int64_t batch_x, int64_t batch_dw, hipStream_t stream) {
+  SSP_CHECK_ARG(route / 100000000 == SSP_WGRAD_LDS && slab_floats > 0, "conv_wgrad_dma (ordered): not an LDS-direct route");
+  WgradArgs a;
+  a.dy = dy; a.x = x; a.dw = ws;
+  a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.lddy = lddy; a.ldx = ldx; a.R = R; a.M = (int)((int64_t)B * H * W);
+  a.batch = batch; a.batch_dy = batch_dy; a.batch_x = batch_x; a.batch_dw = batch_dw;
+  a.store = 1;
+  a.zero_ptr = nullptr;
+  a.zero_bytes = 0;
+  a.nsplit = nsplit; a.chunk_m = chunk_m; a.slab_floats = slab_floats;
+  return wgrad_dma_dispatch(route, a, stream);
 }

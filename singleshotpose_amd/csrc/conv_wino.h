@@ -46,7 +46,8 @@ int ssp_wino_input_launch(const float* in, int ldin, float* V, int B, int H, int
 int ssp_wino_filter_launch(const float* w, float* U, int rows, int K, int tile, hipStream_t stream, bool flip = false);
 int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, int W, int C, int tile, hipStream_t stream,
                             int prof_kind = SSP_PROF_WINO_WGRAD);
-int ssp_wino_wgrad_finish_launch(const float* dU, float* dw, int rows, int K, int tile, hipStream_t stream);
+int ssp_wino_wgrad_finish_launch(const float* dU, float* dw, int rows, int K, int tile, hipStream_t stream, int nslab = 1,
+                                 int64_t slab = 0);
 // adj: the planes are dV of the adjoint data gradient (B dV B^T gathered over the neighbouring tiles) instead of M (A^T M A)
 int ssp_wino_output_launch(const WinoOutArgs& a, int B, int H, int W, int tile, int prof_kind, hipStream_t stream,
                            bool adj = false);

@@ -585,8 +585,11 @@ __global__ void __launch_bounds__(256) wino_outgrad_kernel(const float* __restri
 
 // dw[row][tap][k] += (G^T dU G)[tap]; thread = (row, 4 k's); dw is this launch's own (no other writer): plain read-add-write.
 // Row i of dU at a time: h[b] = sum_j G[j][b] dU[i][j], acc[a][b] += G[i][a] h[b].
+// nslab > 1 (ordered filter gradient): dU is nslab per-pixel-range slabs `slab` floats apart, added element by element in slab
+// order before the back-transform.
 template <int N>
-__global__ void __launch_bounds__(256) wino_wgrad_finish_kernel(const float* __restrict__ dU, float* dw, int rows, int K) {
+__global__ void __launch_bounds__(256) wino_wgrad_finish_kernel(const float* __restrict__ dU, float* dw, int rows, int K, int nslab,
+                                                                int64_t slab) {
   constexpr int A = N + 2;
   using M_ = WinoMat<N>;
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -607,6 +610,9 @@ __global__ void __launch_bounds__(256) wino_wgrad_finish_kernel(const float* __r
     f32x4 u[A];
 #pragma unroll
     for (int j = 0; j < A; ++j) u[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)(i * A + j) * plane);
+    for (int s = 1; s < nslab; ++s)
+#pragma unroll
+      for (int j = 0; j < A; ++j) u[j] = u[j] + *reinterpret_cast<const f32x4*>(src + (int64_t)s * slab + (int64_t)(i * A + j) * plane);
     ssp_sfor<3>([&](auto Bb) {
       constexpr int bb = decltype(Bb)::value;
       f32x4 h = z4;
@@ -660,12 +666,12 @@ int ssp_wino_outgrad_launch(const float* dy, int lddy, float* dM, int B, int H, 
   return SSP_OK;
 }
 
-int ssp_wino_wgrad_finish_launch(const float* dU, float* dw, int rows, int K, int tile, hipStream_t stream) {
+int ssp_wino_wgrad_finish_launch(const float* dU, float* dw, int rows, int K, int tile, hipStream_t stream, int nslab, int64_t slab) {
   SSP_CHECK_ARG(wino_tile_ok(tile), "wino_wgrad_finish: tile must be 2 or 4");
   const int64_t n = (int64_t)rows * (K / 4);
   SspProfScope prof(SSP_PROF_WINO_WGRAD, stream, 4.0 * (double)rows * K * (ssp_wino_planes(tile) + 18.0));
-  if (tile == 2) hipLaunchKernelGGL(wino_wgrad_finish_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dU, dw, rows, K);
-  else hipLaunchKernelGGL(wino_wgrad_finish_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dU, dw, rows, K);
+  if (tile == 2) hipLaunchKernelGGL(wino_wgrad_finish_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dU, dw, rows, K, nslab, slab);
+  else hipLaunchKernelGGL(wino_wgrad_finish_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dU, dw, rows, K, nslab, slab);
   SSP_CHECK_LAUNCH("wino_wgrad_finish");
   return SSP_OK;
 }

@@ -6,6 +6,7 @@
 
 #include "../../include/ssp_hip.h"
 #include "conv_wino.h"
+#include "wgrad_ordered.h"
 #include "conv_bf16x3.h"
 
 // ---- kernels' host launchers (defined next to the kernels) ----
@@ -26,11 +27,13 @@ int ssp_conv_s2_fwd_launch(const float* in, const float* wt, float* out, const f
                            int Cin, int Cout, int ldin, int ldout, int R, int accumulate, const float* escale,
                            float act_slope, hipStream_t stream);
 int ssp_conv_s2_dgrad_launch(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx,
-                             int lddy, int lddx, int R, int accumulate, hipStream_t stream);
+                             int lddy, int lddx, int R, int accumulate, hipStream_t stream, int no_tap_split = 0);
 int ssp_conv_s2_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                              int ldx, int R, hipStream_t stream);
 int ssp_conv_wgrad_wino_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
-                               int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream);
+                               int ldx, int tile, float* ws, int64_t ws_floats, hipStream_t stream, int ordered_split = -1);
+int ssp_wino_wgrad_ordered_split(int B, int H, int W, int Cin, int Cout, int tile, int split);
+int64_t ssp_conv_wgrad_wino_ordered_ws_floats(int B, int H, int W, int Cin, int Cout, int tile, int split);
 int ssp_bn_fwd_finalize_launch(const float* stats, int ntile, int BM, int M, int C, const float* gamma,
                                const float* beta, float* rmean, float* rvar, float momentum, float eps, float* mean,
                                float* invstd, float* scale, float* shift, hipStream_t stream);
@@ -286,6 +289,14 @@ int ssp_conv_dgrad_bnbwd(const float* dy, const float* wt, float* dx, int B, int
     ssp_set_error("conv_dgrad_bnbwd: partial must not be NULL (use ssp_conv_dgrad)");
     return SSP_ERR_ARG;
   }
+  if (partial_rows < 0) {      // no folding: -partial_rows rows, one per tile, or nothing is launched
+    const int ntile = ssp_conv_stats_tiles(B, H, W, Cout_dy, Cin_dx, R, plan);
+    if (ntile > -partial_rows) {
+      ssp_set_error("conv_dgrad_bnbwd: %d tiles do not fit %d rows of partial sums and folding them (fp32 atomics) was refused", ntile, -partial_rows);
+      return SSP_ERR_ARG;
+    }
+    f.nslot = -partial_rows;
+  }
   return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, 0, workspace,
                                workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f, &f);
 }
@@ -318,6 +329,14 @@ int ssp_conv_dgrad_adj_bnbwd(const float* dy, const float* wt, float* dx, int B,
     ssp_set_error("conv_dgrad_adj_bnbwd: partial must not be NULL (use ssp_conv_dgrad_adj)");
     return SSP_ERR_ARG;
   }
+  if (partial_rows < 0) {      // no folding: -partial_rows rows, one per tile, or nothing is launched
+    const int ntile = ssp_conv_stats_tiles(B, H, W, Cout_dy, Cin_dx, R, plan);
+    if (ntile > -partial_rows) {
+      ssp_set_error("conv_dgrad_adj_bnbwd: %d tiles do not fit %d rows of partial sums and folding them (fp32 atomics) was refused", ntile, -partial_rows);
+      return SSP_ERR_ARG;
+    }
+    f.nslot = -partial_rows;
+  }
   return ssp_conv_igemm_launch(dy, wt, dx, nullptr, nullptr, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, 0, workspace,
                                workspace_floats, plan, SSP_PROF_CONV_DGRAD, (hipStream_t)stream, nullptr, 1.f, &f, true, dM);
 }
@@ -346,6 +365,10 @@ int ssp_conv_s2_dgrad(const float* dy, const float* wt, float* dx, int B, int H,
 int ssp_conv_s2_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy, int ldx,
                       int R, void* stream) {
   return ssp_conv_s2_wgrad_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, (hipStream_t)stream);
+}
+int ssp_conv_s2_dgrad_ordered(const float* dy, const float* wt, float* dx, int B, int H, int W, int Cout_dy, int Cin_dx, int lddy,
+                              int lddx, int R, int accumulate, void* stream) {
+  return ssp_conv_s2_dgrad_launch(dy, wt, dx, B, H, W, Cout_dy, Cin_dx, lddy, lddx, R, accumulate, (hipStream_t)stream, 1);
 }
 
 int ssp_bn_act_bwd_partials(const float* x, int ldx, const float* g, int ldg, float* dx, int lddx, const float* scale,
@@ -396,6 +419,45 @@ int ssp_first_bwd_dgrad(const float* x, const float* wt, const float* g, int ldg
 int ssp_conv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
                    int ldx, int R, void* stream) {
   return ssp_conv_wgrad_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, R, (hipStream_t)stream);
+}
+
+// ---- ordered (bitwise-reproducible) filter gradients (wgrad_ordered.h) ----
+int ssp_conv_wgrad_ordered_split(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int stride, int split) {
+  return ssp_wgrad_ordered_plan(B, H, W, Cin, Cout, lddy, ldx, R, stride, split).nsplit;
+}
+int64_t ssp_conv_wgrad_ordered_workspace_floats(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R, int stride,
+                                                int split) {
+  const SspWgradOrderedPlan pl = ssp_wgrad_ordered_plan(B, H, W, Cin, Cout, lddy, ldx, R, stride, split);
+  return (int64_t)pl.nsplit * pl.slab_floats;
+}
+int ssp_conv_wgrad_ordered(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy, int ldx,
+                           int R, int stride, int split, int flags, float* workspace, int64_t workspace_floats, void* stream) {
+  SSP_CHECK_ARG(stride == 1 || stride == 2, "wgrad (ordered): stride must be 1 or 2 (got %d)", stride);
+  SSP_CHECK_ARG(split >= 0 && (flags & ~1) == 0, "wgrad (ordered): split must be >= 0 and flags 0 or 1");
+  SSP_CHECK_ARG(dy != nullptr && x != nullptr && dw != nullptr, "wgrad (ordered): dy / x / dw must not be NULL");
+  SSP_CHECK_ARG(((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)workspace)) & 15) == 0, "wgrad (ordered): dy / x / workspace must be 16-byte aligned");
+  const SspWgradOrderedPlan pl = ssp_wgrad_ordered_plan(B, H, W, Cin, Cout, lddy, ldx, R, stride, split);
+  SSP_CHECK_ARG(pl.nsplit > 0, "wgrad (ordered): shape refused (R 1 | 3, Cin %% 4, leading dimensions %% 4 and >= the channels, < 2^31 pixels)");
+  const int64_t need = (int64_t)pl.nsplit * pl.slab_floats;
+  SSP_CHECK_ARG(workspace != nullptr && workspace_floats >= need,
+                "wgrad (ordered): needs a workspace of %lld floats (ssp_conv_wgrad_ordered_workspace_floats)", (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  SspProfScope prof(SSP_PROF_CONV_WGRAD, st, 2.0 * (double)pl.M * Cout * (double)(R * R * Cin));
+  const int rc = stride == 1 ? ssp_conv_wgrad_ordered_s1_launch(dy, x, workspace, B, H, W, Cin, Cout, lddy, ldx, R, pl, st)
+                             : ssp_conv_s2_wgrad_ordered_launch(dy, x, workspace, B, H, W, Cin, Cout, lddy, ldx, R, pl, st);
+  if (rc != SSP_OK) return rc;
+  return ssp_wgrad_ordered_finish_launch(workspace, dw, pl.slab_floats, pl.nsplit, flags & 1, st);
+}
+int ssp_conv_wgrad_wino_ordered_split(int B, int H, int W, int Cin, int Cout, int tile, int split) {
+  return ssp_wino_wgrad_ordered_split(B, H, W, Cin, Cout, tile, split);
+}
+int64_t ssp_conv_wgrad_wino_ordered_workspace_floats(int B, int H, int W, int Cin, int Cout, int tile, int split) {
+  return ssp_conv_wgrad_wino_ordered_ws_floats(B, H, W, Cin, Cout, tile, split);
+}
+int ssp_conv_wgrad_wino_ordered(const float* dy, const float* x, float* dw, int B, int H, int W, int Cin, int Cout, int lddy,
+                                int ldx, int tile, int split, float* workspace, int64_t workspace_floats, void* stream) {
+  SSP_CHECK_ARG(split >= 0, "wgrad (Winograd, ordered): split must be >= 0");
+  return ssp_conv_wgrad_wino_launch(dy, x, dw, B, H, W, Cin, Cout, lddy, ldx, tile, workspace, workspace_floats, (hipStream_t)stream, split);
 }
 
 int ssp_conv_wgrad_route(int B, int H, int W, int Cin, int Cout, int lddy, int ldx, int R) {

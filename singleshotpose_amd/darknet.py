@@ -83,6 +83,7 @@ class Darknet(nn.Module):
         self._bn_epoch = 0          # bumped by every training-mode forward (engine.Plan: inference BN constants key)
         self._max_plans = 32
         self._conv_math = None      # see conv_math below: None = follow SSP_CONV_MATH
+        self._deterministic = None  # see deterministic below: None = follow SSP_DETERMINISTIC
         # eval forward as one captured hipGraph replay (Plan.forward_graph).  Opt-in: measured no gain on MI355X - the
         # chain is not host-bound (B=1, 672x672: 1.04 ms eager, 36 launches x ~10 us of host time; 1.10 ms replayed)
         self.graph_inference = os.environ.get('SSP_GRAPH_INFERENCE', '0') == '1'
@@ -215,6 +216,22 @@ class Darknet(nn.Module):
         if mode != self.conv_math:
             self._plans.clear()
         self._conv_math = mode
+
+    @property
+    def deterministic(self):
+        """True: the bitwise-reproducible training mode (engine.Plan.deterministic) - every gradient
+        sum in a fixed order, at the price of some speed.  Defaults from SSP_DETERMINISTIC, read when a plan is built;
+        assigning it drops the cached plans, so one model can run both ways - and two models different ways - in one process."""
+        from .engine import knobs
+        return knobs().deterministic if self._deterministic is None else self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        if on not in (True, False, 0, 1):
+            raise ValueError("deterministic %r: expected True or False" % (on,))
+        if bool(on) != self.deterministic:
+            self._plans.clear()
+        self._deterministic = bool(on)
 
     # ---- forward: one autograd node, HIP launches only ----
     def _plan(self, shape, device):

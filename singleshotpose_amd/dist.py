@@ -57,7 +57,7 @@ def sync_plans(model, group=None):
     after the head-error budget; data- and filter-gradient codes after theirs), takes part in ONE broadcast of rank 0's
     codes (a fixed-size message, so that ranks whose plans differ still pair up) and adopts them - all ranks together, or,
     when any rank cannot (another plan shape, a code its environment switched off), all ranks fall back to the library's
-    deterministic heuristic plans for that stage.
+    heuristic plans for that stage (a fixed choice of algorithm).
     Requirement: all ranks build their plans in the same order (same sequence of input shapes) - bench.py and a training
     loop whose multi-scale schedule is seeded identically on every rank; a loop whose ranks draw shapes independently
     must not install it (the broadcasts would pair up wrongly)."""

@@ -235,6 +235,14 @@ class Plan(object):
             raise ValueError("conv_math %r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
         self.conv_math = dict(mode=mode, layers={}, head_deviation=0.0, taken_back=[])
         self._cm_done = False
+        # bitwise-reproducible training mode of this plan, fixed when it is built: the model's attribute
+        # (Darknet.deterministic), else SSP_DETERMINISTIC.  On: every gradient launch whose sum order the hardware would
+        # decide runs its ordered form.  The record (Plan._det_record): layers = {layer: {'wgrad':
+        # (form, route or tile, pixel ranges), 'dgrad': form, 'bn_sums': where the block's BatchNorm-backward sums come
+        # from}}, taken_back = [(layer, what)] fusions the mode undid
+        det = getattr(net, 'deterministic', None)
+        self.deterministic = dict(mode=bool(knobs().deterministic if det is None else det), layers={}, taken_back=[])
+        self._wgrad_ws = None      # slabs of the ordered direct filter gradients: one buffer, they share a stream
         blocks = net.blocks
         self.shapes = layer_shapes(blocks, W, H)  # (w, h, c) per layer
         nl = len(blocks) - 1
@@ -507,6 +515,60 @@ class Plan(object):
         self.consumed = False
         self._graph = self._graph_key = self._x_static = self._y_static = None
         self._graph_failed = False
+        if self.deterministic['mode']:
+            self._plan_bn_fusion()      # (what the record says about the BatchNorm sums; redone with the data-gradient codes)
+            self._det_record()
+
+    # ------------------------------------------------------------------ deterministic mode (SSP_DETERMINISTIC / Darknet.deterministic)
+    def _wgrad_split(self, cs):
+        """(form, route / tile, pixel ranges) of a layer's ordered filter gradient: pure host queries, the library's split -
+        recorded here and passed to the launch explicitly."""
+        B = self.B
+        if cs.first_fused:
+            return ('first-block', 0, _lib.query('ssp_first_groups', B, cs.H, cs.W))      # per-workgroup partials, float64 finalize
+        if cs.wgrad_wino:
+            return ('winograd-ordered', cs.wgrad_wino,
+                    _lib.query('ssp_conv_wgrad_wino_ordered_split', B, cs.H, cs.W, cs.cinp, cs.cout, cs.wgrad_wino, 0))
+        args = (B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.ldraw, cs.inp.ld, cs.k)
+        route = (_lib.query('ssp_conv_wgrad_route', *args) if cs.stride == 1 else
+                 200000000 + 30000000 + (128 if cs.cout > 64 else 64 if cs.cout > 32 else 32) * 1000 +
+                 (128 if cs.cinp > 64 else 64 if cs.cinp > 32 else 32))
+        return ('direct-ordered' if cs.stride == 1 else 'stride2-ordered', route,
+                _lib.query('ssp_conv_wgrad_ordered_split', *(args + (cs.stride, 0))))
+
+    def _det_record(self):
+        rec = self.deterministic
+        if not rec['mode']:
+            return
+        rec['layers'] = {}
+        for i, cs in sorted(self.convs.items()):
+            cs.wgrad_det = self._wgrad_split(cs)
+            if cs.first:
+                dg = 'first-block' if cs.first_fused else 'direct'
+            elif cs.stride == 2:
+                dg = 'stride2-ordered'
+            else:
+                dg = 'plan %d' % cs.plan_dgrad
+            bn = None
+            if cs.bn:
+                bn = ('consumer-dgrad rows=%d' % cs.bnp[1]) if cs.bnp is not None else ('first-block' if cs.first_fused else 'two-level')
+            rec['layers'][i] = dict(wgrad=cs.wgrad_det, dgrad=dg, bn_sums=bn)
+
+    def _wino_ws_query(self, cs, t):
+        """Workspace floats of the layer's Winograd filter gradient at tile value t (the ordered layout in the mode)."""
+        if self.deterministic['mode']:
+            return _lib.query('ssp_conv_wgrad_wino_ordered_workspace_floats', self.B, cs.H, cs.W, cs.cinp, cs.cout, t, 0)
+        return _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', self.B, cs.H, cs.W, cs.cinp, cs.cout, t)
+
+    def _wgrad_ordered_ws(self):
+        """The slabs of the ordered direct filter gradients, allocated on the first backward: sized for the largest layer -
+        the launches of one backward are queued on one stream."""
+        if self._wgrad_ws is None:
+            need = max([1] + [_lib.query('ssp_conv_wgrad_ordered_workspace_floats', self.B, cs.Hi, cs.Wi, cs.cinp, cs.cout,
+                                         cs.ldraw, cs.inp.ld, cs.k, cs.stride, 0)
+                              for cs in self.convs.values() if not cs.first_fused])
+            self._wgrad_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._wgrad_ws
 
     def _place(self, ind, act):
         """acts[ind] = act; the first layer to hold a map is its producer (see _Act)."""
@@ -816,26 +878,31 @@ class Plan(object):
         else:
             mine = [self.convs[i].plan_dgrad for i in order] + [self.convs[i].wgrad_wino for i in order]
         head = [self.B, self.H, self.W, stage, len(order)]
-        got = fn(head + mine)
+        # (deterministic mode: one more entry, so a rank whose mode differs sees a message of another length and every rank
+        # falls back - like a rank with a switched-off code; the mode-off message is unchanged)
+        det = [1] if self.deterministic['mode'] else []
+        got = fn(head + mine + det)
         # Adopt only when EVERY rank can: same plan shape everywhere, and every code one this rank's environment allows
         # (SSP_WINOGRAD / SSP_WINO_TILES / SSP_WINO_FUSED may differ between ranks' launch scripts).  Otherwise all ranks
-        # fall back to the library's heuristic plans (code 0) for this stage - deterministic and the same everywhere.
-        ok = got[:5] == head and len(got) == len(head) + len(mine)
+        # fall back to the library's heuristic plans (code 0) for this stage - a fixed choice of algorithm, the same everywhere.
+        ok = got[:5] == head and len(got) == len(head) + len(mine) + len(det)
         if ok:
             kn = knobs()
-            for k, v in enumerate(got[5:]):
+            for k, v in enumerate(got[5:5 + len(mine)]):
                 if v == mine[k] or v == 0:
                     continue
                 wg = stage == 1 and k >= len(order)                 # (the filter gradients' entries ARE tile sizes)
                 t = (2 if v == WGRAD_FUSED else v) if wg else wino_tile(v)
                 if not form_allowed(kn, t, onchip=(v == WGRAD_FUSED if wg else wino_fused(v))):
                     ok = False
+                if wg and v == WGRAD_FUSED and det:
+                    ok = False       # (the on-chip filter gradient has no ordered form)
                 if not wg and conv_math_of(v) == 'bf16x3' and self.conv_math['mode'] != 'bf16x3':
                     ok = False       # a bf16x3 code and this rank's mode is off: like a Winograd code it switched off
         all_ok = getattr(fn, 'all_ok', None)
         if all_ok is not None:
             ok = all_ok(ok)
-        vals = got[5:] if ok else [0] * len(mine)
+        vals = got[5:5 + len(mine)] if ok else [0] * len(mine)
         for k, i in enumerate(order):
             cs = self.convs[i]
             if stage == 0:
@@ -854,12 +921,13 @@ class Plan(object):
                 if w != cs.wgrad_wino:
                     cs.wgrad_wino = w
                     if w:
-                        cs.wino_ws_floats = _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', self.B, cs.H, cs.W, cs.cinp, cs.cout, w)
+                        cs.wino_ws_floats = self._wino_ws_query(cs, w)
                     cs.wino_ws = None
         if stage == 0:
             self._fit_workspace()
         if self.conv_math['mode'] == 'bf16x3':
             self._conv_math_record()
+        self._det_record()
 
     def _fit_workspace(self):
         need = max([1] + [cs.ws_fwd for cs in self.convs.values()] + [cs.ws_dgrad for cs in self.convs.values()])
@@ -894,7 +962,7 @@ class Plan(object):
     def nbytes_now(self):
         """Bytes of device memory the plan holds right now: forward buffers, and whatever the first backward and the tuner
         added since (gradient buffers, data-gradient operands, Winograd filters and per-layer workspaces)."""
-        ts = self._forward_tensors() + [self._dpack] + [g.t for g in self.grads.values()]
+        ts = self._forward_tensors() + [self._dpack, self._wgrad_ws] + [g.t for g in self.grads.values()]
         for cs in self.convs.values():
             ts += [cs.wbuf, cs.gbuf, cs.wino_ws, cs.first_wpart, cs.bnp[0] if cs.bnp is not None else None]
             ts += list((cs.wino_u or {}).values()) + list((cs.wino_ud or {}).values())
@@ -988,6 +1056,7 @@ class Plan(object):
                 'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
         self._plan_bn_fusion()
         self._fit_workspace()
+        self._det_record()
 
     def _adjoint_rule(self, cs):
         """Whether the layer takes the adjoint form of the data gradient (see _SHARE_DM): its data-gradient plan is a
@@ -1030,6 +1099,12 @@ class Plan(object):
                     cs.inp.ld != scs.ldraw or cs.inp.off != 0 or cs.cin % 4):
                 continue
             ntile = _lib.query('ssp_conv_stats_tiles', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
+            if self.deterministic['mode'] and ntile > 1024:
+                # the fold adds tile t into row t % 1024 with atomics: in the mode the block keeps its own two-level
+                # reduction (ssp_bn_act_bwd: per-workgroup partials, float64 finalize) instead
+                if (src, 'bn-sums-in-dgrad') not in self.deterministic['taken_back']:
+                    self.deterministic['taken_back'].append((src, 'bn-sums-in-dgrad'))
+                continue
             rows = min(ntile, 1024)       # more tiles than rows: folded with atomics into a buffer that stays zeroed
             cs.bn_fuse_src = scs
             scs.bnp = (torch.zeros(rows * scs.cout * 2, dtype=torch.float32, device=self.device), rows, ntile > rows)
@@ -1475,8 +1550,10 @@ class Plan(object):
         if cs.stride == 2:
             # parity-decomposed data gradient (csrc/conv_strided.hip): H x W of the INPUT map, no plan, no workspace, no
             # fused BatchNorm-backward sums (_plan_bn_fusion never makes a strided block the consumer)
-            call('ssp_conv_s2_dgrad', dy_ptr, _ptr(self._dpack, cs.doff), gin.ptr, B, cs.Hi, cs.Wi, cs.coutp, cs.cin, dy_ld,
-                 gin.ld, cs.k, 1 if src in written else 0, st)
+            # (deterministic mode: one thread per pixel on small grids too - their tap split sums with atomics)
+            call('ssp_conv_s2_dgrad_ordered' if self.deterministic['mode'] else 'ssp_conv_s2_dgrad', dy_ptr,
+                 _ptr(self._dpack, cs.doff), gin.ptr, B, cs.Hi, cs.Wi, cs.coutp, cs.cin, dy_ld, gin.ld, cs.k,
+                 1 if src in written else 0, st)
             written.add(src)
             return
         scs = cs.bn_fuse_src
@@ -1488,7 +1565,8 @@ class Plan(object):
             call('ssp_conv_dgrad_adj_bnbwd' if cs.dgrad_adj else 'ssp_conv_dgrad_bnbwd', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W,
                  cs.coutp, cs.cin, dy_ld, gin.ld, cs.k, cs.plan_dgrad, self.ws.data_ptr(), self.ws_floats,
                  scs.raw.data_ptr(), scs.ldraw, sv[2].data_ptr(), sv[3].data_ptr(), sv[0].data_ptr(),
-                 sv[1].data_ptr(), scs.slope, scs.bnp[0].data_ptr(), scs.bnp[1], *adj)
+                 sv[1].data_ptr(), scs.slope, scs.bnp[0].data_ptr(),
+                 -scs.bnp[1] if self.deterministic['mode'] else scs.bnp[1], *adj)      # (< 0: a fold is an error, never atomics)
             fused_stats.add(src)
         else:
             call('ssp_conv_dgrad_adj' if cs.dgrad_adj else 'ssp_conv_dgrad', dy_ptr, dwt, gin.ptr, B, cs.H, cs.W, cs.coutp,
@@ -1779,19 +1857,29 @@ class Plan(object):
         if s.wgrad:
             gw = gview(cs.conv.weight, cs.packed)
             wg_name = 'ssp_conv_s2_wgrad' if cs.stride == 2 else 'ssp_conv_wgrad'      # (both take the INPUT map's H x W)
+            det = self.deterministic['mode']
+
+            def run_direct(dst):
+                if det:      # ordered form: per-range slabs, summed in order (the split is the recorded one)
+                    ows = self._wgrad_ordered_ws()
+                    call('ssp_conv_wgrad_ordered', dy_ptr, cs.inp.ptr, dst, B, cs.Hi, cs.Wi, cs.cinp, cs.cout, dy_ld, cs.inp.ld,
+                         cs.k, cs.stride, cs.wgrad_det[2], 0, ows.data_ptr(), ows.numel(), st2)
+                else:
+                    call(wg_name, dy_ptr, cs.inp.ptr, dst, B, cs.Hi, cs.Wi, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
             if cs.packed and cs.wgrad_wino:
                 wws = self._wino_ws(cs)
                 # (dy = NULL: dM is in its slot of wws already, see above)
-                call('ssp_conv_wgrad_wino_t', None if dm_ptr is not None else dy_ptr, None if cs.v_live else cs.inp.ptr,
-                     gw.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino, wws.data_ptr(),
-                     wws.numel(), st2)
+                wargs = (None if dm_ptr is not None else dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W,
+                         cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.wgrad_wino)
+                if det:
+                    call('ssp_conv_wgrad_wino_ordered', *(wargs + (cs.wgrad_det[2], wws.data_ptr(), wws.numel(), st2)))
+                else:
+                    call('ssp_conv_wgrad_wino_t', *(wargs + (wws.data_ptr(), wws.numel(), st2)))
                 cs.v_live = False
             elif cs.packed:       # accumulate in place: the gradient has the parameter's channels-last layout
-                call(wg_name, dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.Hi, cs.Wi, cs.cinp, cs.cout, dy_ld,
-                     cs.inp.ld, cs.k, st2)
+                run_direct(gw.data_ptr())
             else:
-                call(wg_name, dy_ptr, cs.inp.ptr, self._gbuf(cs).data_ptr(), B, cs.Hi, cs.Wi, cs.cinp,
-                     cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
+                run_direct(self._gbuf(cs).data_ptr())
                 call('ssp_unpack_grad', self._gbuf(cs).data_ptr(), gw.data_ptr(), cs.cout, cs.cin, cs.cinp, cs.k, st2)
             out_grads[id(cs.conv.weight)] = gw
         if params and self.reducer is not None:

@@ -119,7 +119,8 @@ def _finish_pass(n_known):
 
 
 # ---------------------------------------------------------------------- the environment knobs
-Knobs = collections.namedtuple('Knobs', 'autotune verify wino_on tiles min2 min4 fused_on credit_ms wgrad_credit dgrad_credit head_budget tag')
+Knobs = collections.namedtuple('Knobs', 'autotune verify wino_on tiles min2 min4 fused_on credit_ms wgrad_credit dgrad_credit head_budget tag '
+                                         'deterministic')
 
 
 def knobs():
@@ -134,8 +135,14 @@ def knobs():
     tag = the candidate-set tag, part of every tune-cache key: a cache entry written before a family of candidates existed, or
     in a process that had it switched off, must not keep that family from ever being timed - and must not hand a Winograd code
     to a process that switched it off.  It spells the knobs as the environment does (an unset credit as ''): the keys of
-    cfg/bench_tune_cache.json carry it."""
+    cfg/bench_tune_cache.json carry it.
+    deterministic = SSP_DETERMINISTIC (unset, '0' or '1'; anything else is a ValueError): the bitwise-reproducible training
+    mode (engine.Plan.deterministic).  NOT part of the tag: the mode changes no forward or data-gradient
+    candidate, and its filter-gradient decisions live under keys of their own (det_key)."""
     env = os.environ.get
+    det = env('SSP_DETERMINISTIC', '')
+    if det not in ('', '0', '1'):
+        raise ValueError("SSP_DETERMINISTIC=%r: expected unset, 0 or 1" % det)
     wino_on = env('SSP_WINOGRAD', '1') != '0'
     tiles, min2, min4, fused = env('SSP_WINO_TILES', '2,4'), env('SSP_WINO_MIN_CHANNELS', '128'), \
         env('SSP_WINO4_MIN_CHANNELS', '64'), env('SSP_WINO_FUSED', '1')
@@ -145,7 +152,7 @@ def knobs():
                  tiles=tuple(int(t) for t in tiles.split(',') if t), min2=int(min2), min4=int(min4), fused_on=fused != '0',
                  credit_ms=float(env('SSP_ONCHIP_CREDIT_MS', '0.25')), wgrad_credit=float(env('SSP_WGRAD_FUSED_PREFER', '0.8')),
                  dgrad_credit=float(env('SSP_ONCHIP_PREFER', '0.85')), head_budget=float(env('SSP_HEAD_ERR_BUDGET', '3.5e-5')),
-                 tag=tag)
+                 tag=tag, deterministic=det == '1')
 
 
 def _tune_tag():
@@ -218,10 +225,12 @@ def x3_candidates(cs, B, K, N):
     return tuple(c for c in codes if _lib.query('ssp_conv_bf16x3_fits', B, cs.H, cs.W, K, N, cs.k, c))
 
 
-def wgrad_candidates(kn, cs, B):
-    """Winograd forms of the filter gradient timed against the direct kernel (`tile` values of ssp_conv_wgrad_wino_t)."""
+def wgrad_candidates(kn, cs, B, deterministic=False):
+    """Winograd forms of the filter gradient timed against the direct kernel (`tile` values of ssp_conv_wgrad_wino_t).
+    deterministic: the ordered forms (ssp_conv_wgrad_wino_ordered) - tiles 2 and 4; the on-chip form finishes with atomics
+    and has no ordered counterpart, its layers fall to tile 2 / 4 or the direct kernel."""
     tiles, onchip = wino_forms(kn, cs, B, min_channels=64, min_tiles=16, halo_rows=cs.W + 1)
-    return tiles + ((WGRAD_FUSED,) if onchip else ())
+    return tiles + ((WGRAD_FUSED,) if onchip and not deterministic else ())
 
 
 def fwd_key(plan, cs):
@@ -231,6 +240,12 @@ def fwd_key(plan, cs):
 def x3_key(key):
     """The bf16x3 decision of a launch has a key of its own: nothing of the fp32 passes reads it."""
     return (key[0] + '-bf16x3',) + key[1:]
+
+
+def det_key(key):
+    """The deterministic mode's decision of a launch has a key of its own ('wgrad-det', ...): its candidates and kernels are
+    not those of the mode-off decision, and neither reads the other's entry."""
+    return (key[0] + '-det',) + key[1:]
 
 
 def time_launch(launch, repeats):
@@ -490,9 +505,9 @@ def tune_convs(plan, which):
 
 
 # ---------------------------------------------------------------------- the filter-gradient pass
-def _time_wgrad(plan, kn, cs, key, forms, ws_floats, gen):
+def _time_wgrad(plan, kn, cs, key, forms, ws_floats, gen, det=False):
     """The fastest admitted filter-gradient form of one layer (0 = direct): each Winograd form that beats the best so far is
-    verified at once, and a refused one does not move the bar."""
+    verified at once, and a refused one does not move the bar.  det: the ordered entry points, the library's split."""
     B, call, st = plan.B, _lib.call, torch.cuda.current_stream().cuda_stream
     f32 = dict(dtype=torch.float32, device=plan.device)
     ws = torch.empty(ws_floats, **f32)
@@ -502,7 +517,13 @@ def _time_wgrad(plan, kn, cs, key, forms, ws_floats, gen):
     cs.raw.view(-1, cs.ldraw)[:, :cs.cout].uniform_(-1.0, 1.0, generator=gen)
 
     def launch(out, t):
-        if t == 0:
+        if det and t == 0:
+            call('ssp_conv_wgrad_ordered', cs.raw.data_ptr(), cs.inp.ptr, out.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw,
+                 cs.inp.ld, cs.k, 1, 0, 0, ws.data_ptr(), ws.numel(), st)
+        elif det:
+            call('ssp_conv_wgrad_wino_ordered', cs.raw.data_ptr(), cs.inp.ptr, out.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout,
+                 cs.ldraw, cs.inp.ld, t, 0, ws.data_ptr(), ws.numel(), st)
+        elif t == 0:
             call('ssp_conv_wgrad', cs.raw.data_ptr(), cs.inp.ptr, out.data_ptr(), B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw,
                  cs.inp.ld, cs.k, st)
         else:
@@ -538,18 +559,24 @@ def tune_wgrad(plan):
     kn = knobs()
     gen = torch.Generator(device=plan.device).manual_seed(4321)
     n_known = len(_TUNE_CACHE)
+    det = bool(getattr(plan, 'deterministic', None) and plan.deterministic['mode'])
     for cs in plan.convs.values():
         cs.wgrad_wino = 0
-        forms = wgrad_candidates(kn, cs, plan.B)
+        forms = wgrad_candidates(kn, cs, plan.B, det)
         if not forms:
             continue
         key = plan._wgrad_key(cs)
-        wsn = {t: _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', plan.B, cs.H, cs.W, cs.cinp, cs.cout, t) for t in forms}
+        if det:      # ordered candidates, ordered kernels, keys of their own: the two modes' caches never mix
+            key = det_key(key)
+            wsn = {t: _lib.query('ssp_conv_wgrad_wino_ordered_workspace_floats', plan.B, cs.H, cs.W, cs.cinp, cs.cout, t, 0) for t in forms}
+            wsn[0] = _lib.query('ssp_conv_wgrad_ordered_workspace_floats', plan.B, cs.H, cs.W, cs.cinp, cs.cout, cs.ldraw, cs.inp.ld, cs.k, 1, 0)
+        else:
+            wsn = {t: _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', plan.B, cs.H, cs.W, cs.cinp, cs.cout, t) for t in forms}
         cached = _TUNE_CACHE.get(key)
         if cached is not None and (cached == 0 or (cached in forms and (not kn.verify or _TUNE_VERIFIED.get(key) == cached))):
             cs.wgrad_wino = cached
         else:
-            cs.wgrad_wino = _TUNE_CACHE[key] = _TUNE_VERIFIED[key] = _time_wgrad(plan, kn, cs, key, forms, max(wsn.values()), gen)
+            cs.wgrad_wino = _TUNE_CACHE[key] = _TUNE_VERIFIED[key] = _time_wgrad(plan, kn, cs, key, forms, max(wsn.values()), gen, det)
         if cs.wgrad_wino:
             cs.wino_ws_floats = wsn[cs.wgrad_wino]
     _finish_pass(n_known)

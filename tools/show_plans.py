@@ -29,3 +29,11 @@ for ind, cs in sorted(plan.convs.items()):
         ind, cs.H, cs.W, cs.cin, cs.cout, cs.k, cs.plan_fwd, family(cs.plan_fwd), cs.plan_dgrad, family(cs.plan_dgrad),
         ('winograd F(%dx%d)' % (cs.wgrad_wino, cs.wgrad_wino)) if getattr(cs, 'wgrad_wino', 0) else 'direct'))
 print('conv math: %r' % (plan.conv_math,))
+det = plan.deterministic
+print('deterministic: %s' % ('on' if det['mode'] else 'off'))
+for ind, rec in sorted(det['layers'].items()):      # (mode on: form, route code or Winograd tile and pixel ranges of every filter gradient)
+    form, code, nsplit = rec['wgrad']
+    print('layer %2d  wgrad %-16s %-10s ranges %-5d dgrad %-16s bn sums %s' % (
+        ind, form, ('tile %d' % code) if form == 'winograd-ordered' else (code or '-'), nsplit, rec['dgrad'], rec['bn_sums']))
+for ind, what in det['taken_back']:
+    print('layer %2d  taken back: %s' % (ind, what))
