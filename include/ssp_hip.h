@@ -67,6 +67,15 @@ int ssp_set_option(const char* name, int value);
  *   the fp32 kernel.  Non-finite inputs: an Inf operand (or a finite one within half a bf16 ulp of FLT_MAX) gives NaN
  *   where the fp32 kernel gives Inf (Inf - Inf in the split).  Same four entry points; ssp_conv_plan_wino_tile returns
  *   0 and the adjoint entry points refuse the code.
+ *   8000000 | 9000000 + 600000 + tile_rows*100 + 13 (tile_rows 64|128; e.g. 8612813, 9606413) = the Winograd plan
+ *   8000000 | 9000000 + tile_rows*100 + 13 (its "fp32 twin") with its batched GEMM on the bf16x3 kernel: the input,
+ *   output-gradient and filter transforms and both finishing passes are those of the fp32 twin, V, U and M (dM, dV) stay
+ *   fp32 in the workspace, and `wt`, the workspace, the statistics format, ssp_conv_plan_wino_tile (4 | 2) and every query
+ *   answer as for the fp32 twin.  Valid wherever a through-memory Winograd code is: ssp_conv_fwd, ssp_conv_fwd_affine,
+ *   ssp_conv_dgrad, ssp_conv_dgrad_bnbwd, ssp_conv_dgrad_adj and ssp_conv_dgrad_adj_bnbwd (with the caller's dM or its
+ *   own).  Needs R = 3, Cin % 16 == 0, Cout >= 64 and % 4 == 0 (ssp_conv_bf16x3_fits); the hundred-thousands digit of a
+ *   Winograd code must be 0 or 6, the ring digit under 6 must be 3, and a 7xxxxxx code has no such form: everything else is
+ *   an error and nothing is written.  Non-finite inputs as in the direct family: an Inf in V or U gives NaN.
  * stats of a Winograd plan are in the COUNTED format: ssp_conv_stats_tile_m returns 0, the buffer holds
  *   [ssp_conv_stats_tiles(...)][Cout][2] (mean, M2) pairs followed by [ssp_conv_stats_tiles(...)] pixel counts
  *   (ssp_conv_stats_floats floats in all) and ssp_bn_fwd_finalize takes tile_m = 0. */
@@ -98,9 +107,9 @@ int64_t ssp_conv_wino_tiles(int B, int H, int W, int tile);
 int ssp_wino_filter_transform_t(const float* w9, float* U, int rows, int K, int tile, void* stream);
 int ssp_wino_filter_transform(const float* w9, float* U, int rows, int K, void* stream);
 int64_t ssp_conv_workspace_floats(int B, int H, int W, int Cin, int Cout, int R, int plan);
-/* 1 when a launch of that shape runs under the bf16x3 code `plan` (6xxxxxx, above), 0 when the entry points would
- * refuse it (bad code, Cin % 16, Cout <= 32 or % 4, R not 1 | 3, a split with fewer than 8 K-steps, 2^31 pixels or
- * more).  A pure host function: no GPU is touched.  Operand alignment and the workspace are checked by the launch. */
+/* 1 when a launch of that shape runs under the bf16x3 code `plan` (6xxxxxx, or a Winograd twin 8 | 9 6xxxxx, above), 0
+ * when the entry points would refuse it (bad code, Cin % 16, Cout <= 32 or % 4, R not 1 | 3, a split with fewer than 8
+ * K-steps, 2^31 pixels or more; a twin: R not 3, Cin % 16, Cout < 64 or % 4, tile rows not 64 | 128, last digits not 13).  A pure host function: no GPU is touched.  Operand alignment and the workspace are checked by the launch. */
 int ssp_conv_bf16x3_fits(int B, int H, int W, int Cin, int Cout, int R, int plan);
 
 /* data gradient (autograd of nn.Conv2d, train.py:103): dx[p][ci] (+)= sum dy[p - tap][co] * w[co][ci][tap];

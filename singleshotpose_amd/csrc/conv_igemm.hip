@@ -514,6 +514,8 @@ int64_t ssp_conv_ws_floats(int M, int Cin, int Cout, int R, int plan) {
 // transformed input V [P][T][Cin] followed by the GEMM output M [P][T][Cout] (ssp_conv_workspace_floats says how much),
 // and the launch is three kernels: input transform, ONE batched launch of the LDS-direct GEMM kernel (gridDim.y = P), and
 // the finishing pass wino_output_kernel (inverse transform + everything the split-K finish does).
+// Codes with the hundred-thousands digit 6 (8612813, 9606413, ...: conv_bf16x3.h) run the batched GEMM on the bf16x3 kernel
+// instead; V, U and M stay fp32 in memory, so the V a forward leaves for the filter gradient is the same.
 int64_t ssp_wino_ws_floats(int B, int H, int W, int Cin, int Cout, int tile) {
   return ssp_wino_planes(tile) * ssp_wino_tiles(B, H, W, tile) * ((int64_t)Cin + Cout);
 }
@@ -531,8 +533,14 @@ static int wino_launch(ConvArgs& a, int B, int H, int W, float* ws, int64_t ws_f
   const int bm = (plan / 100) % 1000, slots = plan % 10, tile = ssp_wino_plan_tile(plan), P = ssp_wino_planes(tile);
   SSP_CHECK_ARG(a.R == 3 && a.Cin % 16 == 0 && a.Cout >= 64 && a.Cout % 4 == 0 && a.ldout % 4 == 0 && (((uintptr_t)a.out) & 15) == 0,
                 "conv (Winograd plan): needs a 3x3 filter, Cin %% 16 == 0, Cout >= 64 and %% 4 == 0, an aligned output");
+  // hundred-thousands digit 6 (conv_bf16x3.h): the batched GEMM runs on the bf16x3 kernel, whose ring is 3 slots
+  const bool x3 = ssp_bf16x3_wino_plan(plan);
   SSP_CHECK_ARG((bm == 64 || bm == 128) && (slots == 3 || slots == 4 || slots == 8) && (plan / 10) % 10 == 1 &&
-                    (plan / 100000) % 10 == 0, "conv: bad Winograd plan code %d", plan);
+                    ((plan / 100000) % 10 == 0 || x3), "conv: bad Winograd plan code %d", plan);
+  if (x3)      // a code that does not fit its launch is an error, never a quiet run of the fp32 GEMM
+    SSP_CHECK_ARG(ssp_bf16x3_fits(a.M, a.Cin, a.Cout, a.R, plan),
+                  "conv (bf16x3 Winograd plan %d): needs tile rows 64 | 128 and last digits 13 (got Cin %d, Cout %d)", plan,
+                  a.Cin, a.Cout);
   const int64_t T = ssp_wino_tiles(B, H, W, tile);
   SSP_CHECK_ARG(T < (1ll << 31) && P * T * (int64_t)a.Cin < (1ll << 40), "conv (Winograd plan): too many tiles");
   const int64_t need = adj ? ssp_wino_adj_ws_floats(B, H, W, a.Cin, a.Cout, tile, dM == nullptr)
@@ -563,7 +571,9 @@ static int wino_launch(ConvArgs& a, int B, int H, int W, float* ws, int64_t ws_f
   g.ws = nullptr; g.ksplit = 1; g.probe = 0;
   g.bn_partial = nullptr; g.bn_raw = nullptr;
   g.batch = P; g.batch_in = T * a.Cin; g.batch_wt = (int64_t)a.Cout * a.Cin; g.batch_out = T * a.Cout;
-  if (int rc = ssp_conv_igemm_dma_launch(g, bm, slots, 0, prof_kind == SSP_PROF_CONV_DGRAD, stream)) return rc;
+  if (x3) {
+    if (int rc = ssp_bf16x3_launch(g, bm, prof_kind == SSP_PROF_CONV_DGRAD, stream)) return rc;
+  } else if (int rc = ssp_conv_igemm_dma_launch(g, bm, slots, 0, prof_kind == SSP_PROF_CONV_DGRAD, stream)) return rc;
   WinoOutArgs o;
   o.Mw = Mw; o.out = a.out; o.bias = a.bias; o.escale = a.escale; o.act_slope = a.act_slope; o.stats = a.stats;
   o.Cout = a.Cout; o.ldout = a.ldout; o.accumulate = a.accumulate;
@@ -612,6 +622,7 @@ int ssp_conv_igemm_launch(const float* in, const float* wt, float* out, const fl
     return wino_launch(a, B, H, W, ws, ws_floats, plan, prof_kind, stream, true, dM);
   }
   if (ssp_wino_plan_fused(plan)) {
+    SSP_CHECK_ARG((plan / 100000) % 10 != 6, "conv: the on-chip Winograd plans have no bf16x3 form (plan code %d)", plan);
     a.ksplit = 1; a.ws = nullptr;
     return ssp_wino_fused_launch(a, B, H, W, prof_kind, stream);
   }

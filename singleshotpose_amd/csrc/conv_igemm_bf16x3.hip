@@ -1,5 +1,6 @@
 // bf16x3 split-MFMA implicit-GEMM convolution (stride 1, "same" padding, R in {1,3}): the opt-in fast mode of the
-// direct convolutions (plan codes 6000000 + tile_rows * 100 + ksplit * 10 + 3, conv_bf16x3.h).
+// direct convolutions (plan codes 6000000 + tile_rows * 100 + ksplit * 10 + 3, conv_bf16x3.h) and, as a batched R = 1 launch,
+// the GEMM of the through-memory Winograd plans (their twin codes 8 | 9 6xxx13, same header).
 //
 // Same contraction, same operands and same ConvArgs as conv_igemm_kernel (conv_igemm.hip): fp32 NHWC activations and
 // the fp32 packed filter [Cout][R*R][Cin] of ssp_repack_fwd / ssp_repack_dgrad; nothing is pre-split in memory.
@@ -38,6 +39,12 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 // 6 * TM * TN MFMAs of chunk it.  Fragments are read at the top of their chunk (no fragment double buffer: its 48
 // registers pay for the second accumulator; with two workgroups per CU the other wave's MFMAs cover the LDS latency).
 // Loads are branch-free and clamped exactly as there.
+// Batched launch (ConvArgs::batch > 0; the GEMM of the Winograd twin codes, conv_bf16x3.h): blockIdx.y picks the problem,
+// the operand bases move by batch_in / batch_wt floats and the epilogue's output by batch_out; nothing else changes (the
+// loader's rows and the filter rows stay clamped inside their own plane).  Resources with the batch offsets in (hipcc
+// -Rpass-analysis=kernel-resource-usage, gfx950, no scratch): tile rows 128: 228 VGPRs (x 128 columns; 150 x 64) -> 2 waves
+// per SIMD = 2 workgroups per CU, which 72 KiB (54 KiB) of LDS each allow too; tile rows 64: 141 VGPRs (x 128; 90 x 64) ->
+// 3 (5) waves per SIMD by registers, 2 (4) workgroups per CU by their 54 KiB (36 KiB) of LDS.
 // PASS (0 forward, 1 data gradient) only gives the two uses distinct kernel names for profiles.
 template <int BM, int BN, int WM, int WN, int PASS = 0>
 __global__ void __launch_bounds__(WM* WN * 64, 2) conv_igemm_bf16x3_kernel(ConvArgs p) {
@@ -71,6 +78,11 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_igemm_bf16x3_kernel(ConvA
   const int cpt = p.Cin / BK;  // K chunks per filter tap
   const int it_begin = split * p.it_per_split;
   const int niter = min(p.R * p.R * cpt, it_begin + p.it_per_split) - it_begin;   // this workgroup's K chunks
+  // batched launch (the P transform positions of a Winograd layer, conv_wino.hip): blockIdx.y = problem index (scalar);
+  // batch = 0 is one problem at the operands themselves (gridDim.y = 1, every offset 0)
+  const int64_t bz = (p.batch > 0) ? (int64_t)blockIdx.y : 0;
+  const float* const in_b = p.in + bz * p.batch_in;
+  const float* const wt_b = p.wt + bz * p.batch_wt;
 
   // ---- loader setup: rows are fixed for the whole K loop ----
   const int lrow = tid / TPR, lcol = (tid % TPR) * 4;
@@ -82,14 +94,14 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_igemm_bf16x3_kernel(ConvA
     if (m >= p.M) m = p.M - 1;   // clamped duplicate row: computed, never stored
     a_x[i] = m % p.W;
     a_y[i] = (m / p.W) % p.H;
-    a_ptr[i] = p.in + (int64_t)m * p.ldin + lcol;
+    a_ptr[i] = in_b + (int64_t)m * p.ldin + lcol;
   }
   const float* b_ptr[BPASS];
 #pragma unroll
   for (int i = 0; i < BPASS; ++i) {
     int n = n0 + lrow + i * RPP;
     if (n >= p.Cout) n = p.Cout - 1;
-    b_ptr[i] = p.wt + (int64_t)n * K + lcol;
+    b_ptr[i] = wt_b + (int64_t)n * K + lcol;
   }
 
   f32x4 a_reg[APASS], b_reg[BPASS];
@@ -231,7 +243,7 @@ __global__ void __launch_bounds__(WM* WN * 64, 2) conv_igemm_bf16x3_kernel(ConvA
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] += tot[i][j];
 
-  igemm_epilogue<BM, BN, WM, WN, NT>(p, acc, smem, m0, n0, tile_m, split, tid, p.ksplit > 1);
+  igemm_epilogue<BM, BN, WM, WN, NT>(p, acc, smem, m0, n0, tile_m, split, tid, p.ksplit > 1, bz * p.batch_out);
 }
 
 template <int BM, int BN, int PASS>
@@ -243,16 +255,30 @@ static int launch_bf16x3(ConvArgs a, hipStream_t stream) {
   a.ksplit = ssp_cdiv(niter_total, a.it_per_split);
   const int64_t nwg = (int64_t)a.ntile_m * a.ntile_n * a.ksplit;
   SSP_CHECK_ARG(nwg < (1ll << 31), "conv (bf16x3 plan): too many workgroups");
+  if (a.batch > 0) {
+    // a batched launch is the plain GEMM of a Winograd plan: everything else is the finishing pass's work
+    SSP_CHECK_ARG(a.batch <= 65535 && a.R == 1 && a.ksplit == 1 && a.bias == nullptr && a.escale == nullptr &&
+                      a.act_slope == 1.f && a.stats == nullptr && a.bn_partial == nullptr && a.accumulate == 0,
+                  "conv (bf16x3 plan): a batched launch is R = 1, un-split, with no bias, scale, activation, statistics, "
+                  "BatchNorm-backward sums or accumulate");
+    SSP_CHECK_ARG(a.batch_in >= 0 && a.batch_wt >= 0 && a.batch_out >= 0, "conv (bf16x3 plan): negative batch strides");
+  }
   const int lds_bytes = 3 * 3 * (BM + BN) * 16 * 2;
   auto kern = conv_igemm_bf16x3_kernel<BM, BN, 2, 2, PASS>;
   static SspKernelCache cache;   // per instantiation, per device
   if (int rc = ssp_kernel_prepare((const void*)kern, lds_bytes, 256, &cache, nullptr, "conv_igemm_bf16x3")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds_bytes, stream, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg, a.batch > 0 ? a.batch : 1), dim3(256), lds_bytes, stream, a);
   SSP_CHECK_LAUNCH("conv_igemm_bf16x3");
   return SSP_OK;
 }
 
 int ssp_bf16x3_fits(int64_t M, int Cin, int Cout, int R, int plan) {
+  if (ssp_bf16x3_wino_plan(plan)) {      // a through-memory Winograd plan with its batched GEMM on this kernel
+    const int bm = ssp_bf16x3_wino_plan_bm(plan);
+    if ((bm != 64 && bm != 128) || plan % 100 != 13) return 0;      // GEMM digit 1, the kernel's 3-slot ring
+    if (R != 3 || Cin <= 0 || Cin % 16 != 0 || Cout < 64 || Cout % 4 != 0) return 0;
+    return M > 0 && M < (1ll << 31);
+  }
   if (!ssp_bf16x3_plan(plan)) return 0;
   const int bm = ssp_bf16x3_plan_bm(plan), ks = ssp_bf16x3_plan_ksplit(plan);
   if ((bm != 64 && bm != 128) || ks < 1 || plan % 10 != 3) return 0;

@@ -3,7 +3,8 @@
 #include "ssp_common.h"
 
 // Plan codes of the conv entry points: 9000000 + c = F(2x2, 3x3), 8000000 + c = F(4x4, 3x3); c = bm * 100 + 10 + slots is
-// the tile / ring-depth choice of the batched GEMM launch (conv_igemm_dma.hip).
+// the tile / ring-depth choice of the batched GEMM launch (conv_igemm_dma.hip).  + 600000 (slots = 3 only): the same plan with
+// that GEMM on the bf16x3 kernel (conv_bf16x3.h, conv_igemm_bf16x3.hip); transforms, finishing passes and queries unchanged.
 // 7000000 + v = F(2x2, 3x3) with the transform domain kept on the chip (conv_wino_fused.hip): ONE persistent launch, no
 // workspace; same filter operand as a 9xxxxxx plan (tile 2), statistics in the counted format with one group per patch block.
 #define SSP_WINO2_PLAN 9000000

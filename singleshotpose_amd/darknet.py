@@ -202,8 +202,8 @@ class Darknet(nn.Module):
 
     @property
     def conv_math(self):
-        """'fp32' (default) or 'bf16x3': the arithmetic of the direct convolutions (engine.Plan._apply_conv_math, DESIGN.md
-        section 3c).  Defaults from SSP_CONV_MATH, read when a plan is built; assigning it drops the cached plans, so one
+        """'fp32' (default), 'bf16x3': the arithmetic of the direct convolutions, or 'bf16x3-wino': of those and of the batched
+        GEMMs of the through-memory Winograd plans (engine.Plan._apply_conv_math).  Defaults from SSP_CONV_MATH, read when a plan is built; assigning it drops the cached plans, so one
         model can run both ways in one process."""
         from .engine import conv_math_env
         return self._conv_math or conv_math_env()

@@ -32,7 +32,8 @@ from .cfg import layer_shapes, resolve_layers
 from .tuning import (BF16X3, BN_EPS, BN_MOMENTUM, CONV_MATHS, IGEMM_CANDS, IGEMM_LATENCY_CANDS, TUNE_REJECTED,  # noqa: F401
                      WGRAD_FUSED, WINO, WINO4, WINO_GEMM_CANDS, WINOF, _HEAD_BUDGET_CACHE, _HEAD_BUDGET_PINNED, _TUNE_CACHE,
                      _TUNE_CACHE_FILE, _TUNE_FAMILY, _TUNE_VERIFIED, _TUNE_VERIFIED_ALSO, _pad4, _tune_cache_load, _tune_cache_save,
-                     _tune_tag, conv_math_env, conv_math_of, form_allowed, knobs, tune_convs, tune_wgrad, wino_fused, wino_tile, x3_key)
+                     _tune_tag, conv_math_env, conv_math_of, form_allowed, knobs, tune_convs, tune_wgrad, wino_fused, wino_tile, x3_key,
+                     x3_wino, x3_wino_key)
 # (tuning.py holds the plan codes, the process-wide tune state and the passes that choose the codes; bench.py, the tests and
 # the tools reach them as engine.X - the same objects)
 
@@ -195,6 +196,7 @@ class _ConvSpec(object):
     ws_dgrad = 0                   # split-K workspace floats of the data-gradient plan
     fwd_fams = None                # {family: (code, ms)} the head-error budget chooses from
     x3_fwd = x3_dgrad = 0          # bf16x3 mode: the code the tuner admitted for the launch (0 = its fp32 code stays)
+    x3w_fwd = x3w_dgrad = None     # bf16x3-wino mode: {Winograd tile: the twin code the tuner admitted for that family, or 0}
     fp32_fwd = fp32_dgrad = None   # ... and the fp32 code a substituted launch goes back to (None = not substituted)
     stats = None                   # per-tile BatchNorm partial statistics
     first_fused = False
@@ -752,6 +754,11 @@ class Plan(object):
     # kernel fits is moved to a bf16x3 code: with the tuner on the one tuning.tune_convs timed faster than the launch's fp32
     # code and verified (cs.x3_fwd / cs.x3_dgrad), with SSP_AUTOTUNE=0 the code with the tile rows and split of the
     # library's own plan.  Filter gradients, the first block, stride-2 blocks and Winograd launches stay fp32.
+    # Mode 'bf16x3-wino' is that plus: every forward and data-gradient launch (adjoint form included) that ended on a
+    # THROUGH-MEMORY Winograd code is moved to the twin code (tuning.x3_wino_twins: the same plan with its batched GEMM on the
+    # bf16 matrix cores) the tuner timed faster than it and verified (cs.x3w_fwd / cs.x3w_dgrad, per Winograd tile, so the
+    # substitution follows a layer the head budget moves to another family).  With SSP_AUTOTUNE=0 no Winograd plan exists and
+    # the mode equals 'bf16x3'.  The on-chip codes stay fp32.
     def _x3_default(self, cs, which):
         K, N = (cs.cinp, cs.cout) if which == 'fwd' else (cs.coutp, cs.cin)
         args = (self.B, cs.H, cs.W, K, N, cs.k)
@@ -762,6 +769,14 @@ class Plan(object):
             if _lib.query('ssp_conv_bf16x3_fits', *(args + (code,))):
                 return code
         return 0
+
+    def _x3_wino_code(self, cs, which):
+        """Mode 'bf16x3-wino': the twin code the tuner admitted for the Winograd family the launch ended on; 0 = none, the
+        on-chip form, or another mode."""
+        code = cs.plan_fwd if which == 'fwd' else cs.plan_dgrad
+        if self.conv_math['mode'] != 'bf16x3-wino' or wino_fused(code):
+            return 0
+        return ((cs.x3w_fwd if which == 'fwd' else cs.x3w_dgrad) or {}).get(wino_tile(code), 0)
 
     def _conv_math_record(self):
         self.conv_math['layers'] = {i: (cs.plan_fwd, cs.plan_dgrad) for i, cs in sorted(self.convs.items())
@@ -792,15 +807,18 @@ class Plan(object):
         only ever infers - on its first forward, in that forward's mode."""
         self._cm_done = True
         rec = self.conv_math
-        if rec['mode'] != 'bf16x3':
+        if rec['mode'] == 'fp32':
             return
         self._conv_math_revert()
         rec.update(layers={}, head_deviation=0.0, taken_back=[])
         subs = []
         for ind, cs in sorted(self.convs.items()):
-            if cs.first or cs.stride != 1 or wino_tile(cs.plan_fwd):
+            if cs.first or cs.stride != 1:
                 continue
-            code = cs.x3_fwd if self._tune else self._x3_default(cs, 'fwd')
+            if wino_tile(cs.plan_fwd):
+                code = self._x3_wino_code(cs, 'fwd')
+            else:
+                code = cs.x3_fwd if self._tune else self._x3_default(cs, 'fwd')
             if code:
                 subs.append((cs, code))
 
@@ -853,14 +871,17 @@ class Plan(object):
         """The data-gradient substitutions (Plan._prepare_backward, after the tuner): the layers the head budget took back
         keep fp32 in both directions."""
         rec = self.conv_math
-        if rec['mode'] != 'bf16x3':
+        if rec['mode'] == 'fp32':
             return
         for ind, cs in sorted(self.convs.items()):
             if cs.fp32_dgrad is not None:
                 cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
-            if cs.first or cs.stride != 1 or wino_tile(cs.plan_dgrad) or ind in rec['taken_back']:
+            if cs.first or cs.stride != 1 or ind in rec['taken_back']:
                 continue
-            code = cs.x3_dgrad if self._tune else self._x3_default(cs, 'dgrad')
+            if wino_tile(cs.plan_dgrad):
+                code = self._x3_wino_code(cs, 'dgrad')
+            else:
+                code = cs.x3_dgrad if self._tune else self._x3_default(cs, 'dgrad')
             if code:
                 cs.fp32_dgrad, cs.plan_dgrad = cs.plan_dgrad, code
         self._conv_math_record()
@@ -897,7 +918,8 @@ class Plan(object):
                     ok = False
                 if wg and v == WGRAD_FUSED and det:
                     ok = False       # (the on-chip filter gradient has no ordered form)
-                if not wg and conv_math_of(v) == 'bf16x3' and self.conv_math['mode'] != 'bf16x3':
+                if not wg and conv_math_of(v) == 'bf16x3' and self.conv_math['mode'] not in (
+                        ('bf16x3-wino',) if x3_wino(v) else ('bf16x3', 'bf16x3-wino')):
                     ok = False       # a bf16x3 code and this rank's mode is off: like a Winograd code it switched off
         all_ok = getattr(fn, 'all_ok', None)
         if all_ok is not None:
@@ -925,7 +947,7 @@ class Plan(object):
                     cs.wino_ws = None
         if stage == 0:
             self._fit_workspace()
-        if self.conv_math['mode'] == 'bf16x3':
+        if self.conv_math['mode'] != 'fp32':
             self._conv_math_record()
         self._det_record()
 
@@ -1044,6 +1066,10 @@ class Plan(object):
                 xkey = x3_key(key)
                 xcode = _TUNE_CACHE.get(xkey, 0)
                 cs.x3_dgrad = xcode if xcode and _TUNE_VERIFIED.get(xkey) == xcode else 0
+                t = wino_tile(cs.plan_dgrad)
+                wkey = x3_wino_key(key, t)
+                wcode = _TUNE_CACHE.get(wkey, 0)
+                cs.x3w_dgrad = {t: wcode} if t and wcode and _TUNE_VERIFIED.get(wkey) == wcode else None
         self._conv_math_dgrad()              # bf16x3 mode: the direct data-gradient launches the kernel fits
         if tune:
             self._sync_codes(1)              # multi-GPU: ... and rank 0's data- / filter-gradient choices

@@ -29,19 +29,36 @@ WINO_GEMM_CANDS = (6413, 6414, 12813, 12814)
 # bf16x3 fast mode of the direct kernel (csrc/conv_igemm_bf16x3.hip): plan codes BF16X3 + tile_rows*100 + ksplit*10 + 3.
 # Opt-in (SSP_CONV_MATH=bf16x3 / Darknet.conv_math); with the mode off no such code is ever timed, cached or run.
 BF16X3 = 6000000
-CONV_MATHS = ('fp32', 'bf16x3')
+# ... and of the batched GEMM of a through-memory Winograd plan: the plan's code + X3_WINO with GEMM code tile_rows*100 + 13
+# (8612813, 9606413, ...: its "twin").  Only under SSP_CONV_MATH=bf16x3-wino, which is 'bf16x3' plus these.
+X3_WINO = 600000
+X3_WINO_GEMM_CANDS = (12813, 6413)
+CONV_MATHS = ('fp32', 'bf16x3', 'bf16x3-wino')
 BN_EPS = 1e-4        # darknet.py:157
 BN_MOMENTUM = 0.1    # nn.BatchNorm2d default
 NEAR_TIE = 0.985     # a later candidate must be this much faster than the best so far: near-ties go to the earlier (simpler) one
 
 
+def x3_wino(code):
+    """True for the twin codes: a through-memory Winograd plan (8xxxxxx / 9xxxxxx) with its GEMM on the bf16 matrix cores."""
+    return 8000000 <= code < 10000000 and (code // 100000) % 10 == 6
+
+
 def conv_math_of(code):
-    """'bf16x3' for a 6xxxxxx plan code, 'fp32' for every other (direct and Winograd) code."""
-    return 'bf16x3' if BF16X3 <= code < BF16X3 + 1000000 else 'fp32'
+    """'bf16x3' for a 6xxxxxx plan code and for a Winograd twin code (x3_wino tells the two families apart), 'fp32' for every
+    other (direct and Winograd) code."""
+    return 'bf16x3' if BF16X3 <= code < BF16X3 + 1000000 or x3_wino(code) else 'fp32'
+
+
+def x3_wino_twins(code):
+    """The twin codes of a through-memory fp32 Winograd code, tile rows 128 then 64; () for every other code."""
+    if not wino_tile(code) or wino_fused(code) or (code // 100000) % 10:
+        return ()
+    return tuple(code - code % 100000 + X3_WINO + c for c in X3_WINO_GEMM_CANDS)
 
 
 def conv_math_env():
-    """SSP_CONV_MATH: 'fp32' (default, also when unset or empty) or 'bf16x3'."""
+    """SSP_CONV_MATH: 'fp32' (default, also when unset or empty), 'bf16x3' or 'bf16x3-wino'."""
     mode = os.environ.get('SSP_CONV_MATH', '') or 'fp32'
     if mode not in CONV_MATHS:
         raise ValueError("SSP_CONV_MATH=%r: expected one of %s" % (mode, ', '.join(CONV_MATHS)))
@@ -240,6 +257,12 @@ def fwd_key(plan, cs):
 def x3_key(key):
     """The bf16x3 decision of a launch has a key of its own: nothing of the fp32 passes reads it."""
     return (key[0] + '-bf16x3',) + key[1:]
+
+
+def x3_wino_key(key, tile):
+    """... and so has the twin decision of a launch, per Winograd tile (a forward launch may be moved between the families by
+    the head budget: each family's decision is made, and kept, on its own)."""
+    return (key[0] + '-bf16x3-wino',) + key[1:] + (tile,)
 
 
 def det_key(key):
@@ -473,6 +496,34 @@ def _tune_x3(plan, kn, sc, cs, probe, key, K, N, fp32_code):
     return admit(kn, sc.gen, _TUNE_CACHE[key], key, probe)
 
 
+def x3_wino_launches(plan, cs, which):
+    """[(tile, tune key, fp32 Winograd code)] of the twin decisions of a layer's forward / data-gradient launch: the
+    through-memory Winograd code the launch ended on and, forward, the one of every other family the head budget may move the
+    layer to (cs.fwd_fams) - those whose twins the kernel fits."""
+    if which == 'dgrad':
+        key, codes, K, N = plan._dgrad_key(cs), [cs.plan_dgrad], cs.coutp, cs.cin
+    else:
+        key, K, N = fwd_key(plan, cs), cs.cinp, cs.cout
+        codes = [cs.plan_fwd] + [c for f, (c, _) in sorted((cs.fwd_fams or {}).items()) if f != wino_tile(cs.plan_fwd)]
+    out = []
+    for code in codes:
+        twins = x3_wino_twins(code)
+        if twins and not cs.first and _lib.query('ssp_conv_bf16x3_fits', plan.B, cs.H, cs.W, K, N, cs.k, twins[0]):
+            out.append((wino_tile(code), x3_wino_key(key, wino_tile(code)), code))
+    return out
+
+
+def _tune_x3_wino(plan, kn, sc, cs, probe, key, fp32_code):
+    """bf16x3-wino mode, after (and apart from) the fp32 decisions and the head budget's families: the Winograd code against its
+    twins, same timing, near-ties to fp32, verified against plan 0 at the Winograd 3e-5.  Plan._apply_conv_math /
+    _conv_math_dgrad substitute."""
+    if key not in _TUNE_CACHE:
+        probe.prep(wino_tile(fp32_code))
+        timed = [(code, time_launch(lambda: probe.launch(code), 2)) for code in (fp32_code,) + x3_wino_twins(fp32_code)]
+        _TUNE_CACHE[key] = select(kn, key[0], [(0, timed[0][1])] + timed[1:])[0]      # (0 = the fp32 code stays)
+    return admit(kn, sc.gen, _TUNE_CACHE[key], key, probe)
+
+
 def tunable(plan):
     """The layers whose forward / data-gradient launches take plan codes: stride 1, input channels a multiple of 16."""
     return [cs for cs in plan.convs.values() if cs.cinp % 16 == 0 and cs.stride == 1]
@@ -497,10 +548,18 @@ def tune_convs(plan, which):
         cands = conv_candidates(kn, cs, plan.B, which)
         if cands is not None:
             tune(plan, kn, sc, cs, probes[cs.ind], *cands)
-    for cs in elig if plan.conv_math['mode'] == 'bf16x3' else ():
+    for cs in elig if plan.conv_math['mode'] != 'fp32' else ():
         x3 = x3_launch(plan, cs, which)
         if x3 is not None:
             setattr(cs, 'x3_' + which, _tune_x3(plan, kn, sc, cs, probes[cs.ind], *x3))
+    for cs in elig if plan.conv_math['mode'] == 'bf16x3-wino' else ():
+        setattr(cs, 'x3w_' + which, {t: _tune_x3_wino(plan, kn, sc, cs, probes[cs.ind], key, code)
+                                     for t, key, code in x3_wino_launches(plan, cs, which)})
+        # (the forward's transformed filters of a family the layer is not on go back to the allocator, as after the fp32 pass)
+        if which == 'fwd':
+            cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
+        else:
+            cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
     _finish_pass(n_known)
 
 

@@ -29,7 +29,8 @@ def main():
     ap.add_argument('--wvariants', default='', help='comma list of wgrad_variant values to loop over')
     ap.add_argument('--variants', default='', help='comma list: run every case once per igemm_variant value')
     ap.add_argument('--plans', default='0', help='comma list of explicit plan codes for fwd / dgrad (0 = heuristic; 9006413 etc. = '
-                                                 'Winograd: filters are transformed first, outside the timed launches)')
+                                                 'Winograd: filters are transformed first, outside the timed launches; 8612813 etc. = '
+                                                 'the bf16x3 twin of a Winograd plan)')
     ap.add_argument('--err', action='store_true', help='also print the forward / data-gradient error of every row against a float64 '
                                                        'evaluation of 4096 sampled output pixels (rms and max, relative to the output range)')
     ap.add_argument('--stats', default='unit', choices=['unit', 'net'], help="operand statistics: unit = uniform(-1, 1) everywhere; "
@@ -160,7 +161,9 @@ def run_cases(args, dev, st, B):
                     continue
                 if (op == 'dgrad' and name == 'l0') or (op == 'wfilt' and not wino) or (op == 'wgrad' and plan != int(args.plans.split(',')[0])) or (op == 'wgradw' and wsw is ws):
                     continue
-                if 6000000 <= plan < 7000000 and op in ('fwd', 'dgrad') and not _lib.query(      # bf16x3 codes: a misfit is an error
+                # bf16x3 codes (6xxxxxx, and the Winograd twins 8 / 9 6xxxxx = that plan with its GEMM on the bf16 matrix cores): a misfit is an error
+                x3 = 6000000 <= plan < 7000000 or (plan >= 8000000 and (plan // 100000) % 10 == 6)
+                if x3 and op in ('fwd', 'dgrad') and not _lib.query(
                         'ssp_conv_bf16x3_fits', B, H, W, *((Cin, Cout) if op == 'fwd' else (coutp, Cin)), R, plan):
                     continue
                 fn = fns[op]

@@ -1,16 +1,19 @@
 #!/usr/bin/env python
 """Prints the autotuned igemm plan of every conv launch of cfg/yolo-pose.cfg at a given batch / size
 (plan code = tail*100000 + tile_rows*100 + ksplit*10 + ring_slots; 0 = library heuristic; 9xxxxxx = Winograd F(2x2), 8xxxxxx = Winograd F(4x4),
-7xxxxxx = on-chip F(2x2), 6xxxxxx = bf16x3 (6000000 + tile_rows*100 + ksplit*10 + 3; only with SSP_CONV_MATH=bf16x3))."""
+7xxxxxx = on-chip F(2x2), 6xxxxxx = bf16x3 (6000000 + tile_rows*100 + ksplit*10 + 3; only with SSP_CONV_MATH=bf16x3 / bf16x3-wino),
+86xxxxx / 96xxxxx = a Winograd plan with its batched GEMM on the bf16x3 kernel (only with SSP_CONV_MATH=bf16x3-wino))."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from singleshotpose_amd.darknet import Darknet
-from singleshotpose_amd.engine import conv_math_of, wino_fused, wino_tile
+from singleshotpose_amd.engine import conv_math_of, wino_fused, wino_tile, x3_wino
 
 
 def family(code):
+    if x3_wino(code):      # a Winograd plan with its batched GEMM on the bf16 matrix cores (only with SSP_CONV_MATH=bf16x3-wino)
+        return 'F(%dx%d) bf16x3' % (wino_tile(code), wino_tile(code))
     if conv_math_of(code) == 'bf16x3':
         return 'bf16x3'
     if wino_fused(code):
