@@ -187,6 +187,7 @@ class _ConvSpec(object):
     kind = 'conv'
     _raw = None
     _raw_spec = None     # (allocator, floats, tensor kwargs)
+    plan_fwd = plan_dgrad = 0      # explicit igemm plan codes (0 = library heuristic): changed through Plan.set_code alone
     # set later, by the tuner, the first forward / backward or _plan_bn_fusion
     wbuf = gbuf = None             # forward-operand / filter-gradient staging of a parameter that is not channels-last
     wino_u = wino_ud = None        # {tile: Winograd-transformed forward / data-gradient filters}
@@ -362,7 +363,6 @@ class Plan(object):
                 else:
                     cs.out = _Act(cs.raw, 0, c, cs.H, cs.W, cs.coutp)
                 cs.out.flat = t == 'connected'
-                cs.plan_fwd = cs.plan_dgrad = 0     # explicit igemm plan codes (0 = library heuristic), see tuning.tune_convs
                 # per-channel vectors: mean, invstd, scale, shift, c1, c2, dgamma, dbeta
                 cs.vec = torch.zeros(8, cs.coutp, **f32)
                 if not cs.bn:
@@ -457,6 +457,7 @@ class Plan(object):
         self._dgrad_fallback = False     # Plan.backward's no-tuning fallback made its choices (once per plan)
         self.bn_partial = torch.empty(_lib.query('ssp_bn_bwd_blocks') * 2 * max(cs.coutp for cs in self.convs.values()), **f32)
         self._tune = device.type == 'cuda' and knobs().autotune
+        self._stale = set()        # what set_code changed since the last _settle: 'fwd' / 'dgrad'
         if self._tune:
             tune_convs(self, 'fwd')
         # statistics / split-K workspaces follow the (tuned or heuristic) plan of each launch
@@ -478,6 +479,7 @@ class Plan(object):
         # split-K partial tiles (13x13 layers): one scratch buffer shared by every conv launch of the plan
         self.ws_floats = max([1] + [cs.ws_fwd for cs in self.convs.values()])
         self.ws = torch.empty(self.ws_floats, **f32)
+        self._stale.clear()        # (everything above was sized for the tuned codes: nothing to settle)
         self._head_budget_done = False
         self._hb_gains = None
         self._hb_gains_after_forward = False
@@ -602,6 +604,60 @@ class Plan(object):
         if cs.bn and (cs.stats is None or cs.stats.numel() < nstat):
             cs.stats = torch.empty(nstat, dtype=torch.float32, device=self.device)
 
+    # ------------------------------------------------------------------ plan codes: one writer, one settle step
+    def set_code(self, cs, which, code, fp32=None):
+        """The one place a launch's code changes.  which = 'fwd' / 'dgrad': the plan code and the fp32 code a substituted launch
+        goes back to (None = not substituted; kept for a bf16x3 code only: an fp32 code needs none); 'wgrad': the filter
+        gradient's form (0 = direct, else the Winograd tile or WGRAD_FUSED).  What follows for the layer alone is done at
+        once; what follows for the plan waits for _settle, which the caller runs once per group of writes."""
+        if which == 'wgrad':
+            if code != cs.wgrad_wino:
+                cs.wgrad_wino = code
+                if code:
+                    cs.wino_ws_floats = self._wino_ws_query(cs, code)
+                cs.wino_ws = None
+                self._stale.add('dgrad')
+            return
+        fp32 = fp32 if conv_math_of(code) == 'bf16x3' else None
+        if which == 'fwd' and (code, fp32) != (cs.plan_fwd, cs.fp32_fwd):
+            cs.plan_fwd, cs.fp32_fwd = code, fp32
+            self._size_layer(cs)
+            self._stale.add('fwd')
+        elif which == 'dgrad' and (code, fp32) != (cs.plan_dgrad, cs.fp32_dgrad):
+            cs.plan_dgrad, cs.fp32_dgrad = code, fp32
+            self._stale.add('dgrad')
+
+    def _settle(self, dgrad=False):
+        """Brings the plan-wide state up to date with the codes, once per group of set_code calls (a workspace that grows
+        synchronises the stream).  After a data-gradient code or a filter-gradient form changed (dgrad=True: or on their
+        first sizing): the split-K need of every data gradient and the BatchNorm-backward fusion, whose buffers follow the
+        data-gradient tiles.  After a forward code changed or a transformed forward filter was released: a captured
+        inference chain holds the old codes and pointers - the next forward_graph call captures again."""
+        stale, self._stale = self._stale, set()
+        if dgrad or 'dgrad' in stale:
+            for cs in self.convs.values():
+                cs.ws_dgrad = 0 if (cs.first or cs.stride == 2) else _lib.query(
+                    'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
+            self._plan_bn_fusion()
+        self._fit_workspace()
+        if 'fwd' in stale:
+            self._graph = None
+        self._conv_math_record()
+        self._det_record()
+
+    def _release_filters(self, which, layers):
+        """The transformed forward / data-gradient filters of the tile sizes a layer's launch is not on go back to the allocator:
+        after the layer was tuned and at the end of _apply_head_budget (whose forwards re-use them); _settle follows."""
+        for cs in layers:
+            have = (cs.wino_u if which == 'fwd' else cs.wino_ud) or {}
+            keep = {t: b for t, b in have.items() if t == wino_tile(cs.plan_fwd if which == 'fwd' else cs.plan_dgrad)}
+            if which == 'fwd':
+                cs.wino_u = keep
+                if len(keep) < len(have):
+                    self._stale.add('fwd')
+            else:
+                cs.wino_ud = keep
+
     def _apply_head_budget(self):
         """Error-aware admission of the forward plans: a NETWORK-level rounding budget, measured on the live batch.
 
@@ -656,9 +712,8 @@ class Plan(object):
 
             def run(assign):
                 for cs in cand:
-                    cs.plan_fwd = assign[cs.ind]
-                    self._size_layer(cs)
-                self._fit_workspace()
+                    self.set_code(cs, 'fwd', assign[cs.ind])
+                self._settle()
                 self._forward_body(True, False, False, bn_force=True)
                 return head()
             mom, self.bn_momentum = self.bn_momentum, 0.0
@@ -698,10 +753,9 @@ class Plan(object):
                 _HEAD_BUDGET_PINNED[pkey][-1] = int(round(rec['head_deviation'] * 1e12))
                 _tune_cache_save()
         for cs in cand:
-            cs.plan_fwd = rec['chosen'].get(cs.ind, cs.plan_fwd)
-            self._size_layer(cs)
-            cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
-        self._fit_workspace()
+            self.set_code(cs, 'fwd', rec['chosen'].get(cs.ind, cs.plan_fwd))
+        self._release_filters('fwd', cand)
+        self._settle()
         self.head_budget = rec
         # the amplification the decisions were measured under (head_budget_drifted).  A record adopted from the cache ran no
         # measurement forward here: the scale vectors of this batch exist only after the forward body (forward() takes them)
@@ -729,10 +783,9 @@ class Plan(object):
                 fams = cs.fwd_fams
                 if fams:
                     best = min((v for v in fams.values() if v[1] is not None), key=lambda v: v[1], default=None)
-                    if best is not None and best[0] != cs.plan_fwd:
-                        cs.plan_fwd = best[0]
-                        self._size_layer(cs)
-            self._fit_workspace()
+                    if best is not None:
+                        self.set_code(cs, 'fwd', best[0])
+            self._settle()
 
     def _bn_gains(self):
         bn = [cs for _, cs in sorted(self.convs.items()) if cs.bn]
@@ -770,33 +823,37 @@ class Plan(object):
                 return code
         return 0
 
-    def _x3_wino_code(self, cs, which):
-        """Mode 'bf16x3-wino': the twin code the tuner admitted for the Winograd family the launch ended on; 0 = none, the
-        on-chip form, or another mode."""
-        code = cs.plan_fwd if which == 'fwd' else cs.plan_dgrad
-        if self.conv_math['mode'] != 'bf16x3-wino' or wino_fused(code):
+    @staticmethod
+    def _own_code(cs, which):
+        """The launch's own fp32 code: the one it runs, or goes back to while it is substituted."""
+        code, fp32 = (cs.plan_fwd, cs.fp32_fwd) if which == 'fwd' else (cs.plan_dgrad, cs.fp32_dgrad)
+        return code if fp32 is None else fp32
+
+    def _x3_code(self, cs, which):
+        """The rule above as one function of a layer's forward / data-gradient launch: the code to run instead of the
+        launch's own fp32 code, or 0 = that one stays."""
+        if self.conv_math['mode'] == 'fp32' or cs.first or cs.stride != 1:
             return 0
-        return ((cs.x3w_fwd if which == 'fwd' else cs.x3w_dgrad) or {}).get(wino_tile(code), 0)
+        own = self._own_code(cs, which)
+        if wino_tile(own):
+            if self.conv_math['mode'] != 'bf16x3-wino' or wino_fused(own):
+                return 0
+            return ((cs.x3w_fwd if which == 'fwd' else cs.x3w_dgrad) or {}).get(wino_tile(own), 0)
+        if self._tune:
+            return cs.x3_fwd if which == 'fwd' else cs.x3_dgrad
+        return self._x3_default(cs, which)
 
     def _conv_math_record(self):
         self.conv_math['layers'] = {i: (cs.plan_fwd, cs.plan_dgrad) for i, cs in sorted(self.convs.items())
                                     if 'bf16x3' in (conv_math_of(cs.plan_fwd), conv_math_of(cs.plan_dgrad))}
 
-    def _conv_math_revert(self):
-        """Every substituted launch back on its fp32 code (what the head budget measures, and measures against)."""
-        fwd = [cs for cs in self.convs.values() if cs.fp32_fwd is not None]
-        dgrad = [cs for cs in self.convs.values() if cs.fp32_dgrad is not None]
-        for cs in fwd:
-            cs.plan_fwd, cs.fp32_fwd = cs.fp32_fwd, None
-            self._size_layer(cs)
-        for cs in dgrad:
-            cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
-        if dgrad:
-            self._dgrad_sizes()
-        if fwd or dgrad:
-            self._fit_workspace()
-            self._graph = None           # a captured inference chain holds the old codes
-            self._conv_math_record()
+    def _conv_math_revert(self, which=None):
+        """Every substituted launch (of one direction, or of both) back on its fp32 code: what the head budget measures and
+        measures against, and what the data-gradient choices start from."""
+        for w in ('fwd', 'dgrad') if which is None else (which,):
+            for cs in self.convs.values():
+                self.set_code(cs, w, self._own_code(cs, w))
+        self._settle()
 
     def _apply_conv_math(self, training):
         """The forward substitutions and their budget: one forward on the live batch measures the head deviation d the
@@ -811,24 +868,12 @@ class Plan(object):
             return
         self._conv_math_revert()
         rec.update(layers={}, head_deviation=0.0, taken_back=[])
-        subs = []
-        for ind, cs in sorted(self.convs.items()):
-            if cs.first or cs.stride != 1:
-                continue
-            if wino_tile(cs.plan_fwd):
-                code = self._x3_wino_code(cs, 'fwd')
-            else:
-                code = cs.x3_fwd if self._tune else self._x3_default(cs, 'fwd')
-            if code:
-                subs.append((cs, code))
+        subs = [cs for _, cs in sorted(self.convs.items()) if self._x3_code(cs, 'fwd')]
 
-        def assign(cs, code):
-            if code:
-                cs.fp32_fwd, cs.plan_fwd = cs.plan_fwd, code
-            else:
-                cs.plan_fwd, cs.fp32_fwd = cs.fp32_fwd, None
-            self._size_layer(cs)
-            self._fit_workspace()
+        def substitute():
+            for cs in subs:
+                self.set_code(cs, 'fwd', self._x3_code(cs, 'fwd'), cs.plan_fwd)
+            self._settle()
 
         budget = knobs().head_budget
         if subs and budget > 0:
@@ -846,45 +891,31 @@ class Plan(object):
             try:
                 ref = head()
                 den = max(float(ref.abs().max()), 1e-30)
-                for cs, code in subs:
-                    assign(cs, code)
+                substitute()
                 while True:
                     d = float((head() - ref).abs().max()) / den
                     if not subs or (base * base + d * d) ** 0.5 <= budget:      # (false for NaN: everything goes back)
                         break
-                    cs, _ = subs.pop(0)
-                    assign(cs, 0)
+                    cs = subs.pop(0)
+                    self.set_code(cs, 'fwd', cs.fp32_fwd)
+                    self._settle()
                     rec['taken_back'].append(cs.ind)
                 rec['head_deviation'] = d
             finally:
                 self.bn_momentum = mom
         else:
-            for cs, code in subs:
-                assign(cs, code)
-        self._graph = None
+            substitute()
         if self._dgrad_fallback:         # the data-gradient choices exist already (a re-measurement): same layers there
             self._conv_math_dgrad()
-            self._dgrad_sizes()
-        self._conv_math_record()
+            self._settle()
 
     def _conv_math_dgrad(self):
-        """The data-gradient substitutions (Plan._prepare_backward, after the tuner): the layers the head budget took back
-        keep fp32 in both directions."""
-        rec = self.conv_math
-        if rec['mode'] == 'fp32':
-            return
+        """The data-gradient substitutions (Plan._prepare_backward, after the tuner; the caller settles): the layers the head
+        budget took back keep fp32 in both directions."""
         for ind, cs in sorted(self.convs.items()):
-            if cs.fp32_dgrad is not None:
-                cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
-            if cs.first or cs.stride != 1 or ind in rec['taken_back']:
-                continue
-            if wino_tile(cs.plan_dgrad):
-                code = self._x3_wino_code(cs, 'dgrad')
-            else:
-                code = cs.x3_dgrad if self._tune else self._x3_default(cs, 'dgrad')
-            if code:
-                cs.fp32_dgrad, cs.plan_dgrad = cs.plan_dgrad, code
-        self._conv_math_record()
+            own = self._own_code(cs, 'dgrad')
+            code = 0 if ind in self.conv_math['taken_back'] else self._x3_code(cs, 'dgrad')
+            self.set_code(cs, 'dgrad', code or own, own)
 
     def _sync_codes(self, stage):
         """Multi-GPU: adopt rank 0's plan codes (singleshotpose_amd.dist.sync_plans installs the hook on the model).
@@ -927,29 +958,13 @@ class Plan(object):
         vals = got[5:5 + len(mine)] if ok else [0] * len(mine)
         for k, i in enumerate(order):
             cs = self.convs[i]
+            # (an adopted bf16x3 code keeps this rank's own fp32 code to go back to)
             if stage == 0:
-                if vals[k] != cs.plan_fwd:
-                    # (an adopted bf16x3 code keeps this rank's fp32 code to go back to; an adopted fp32 code needs none)
-                    own = cs.fp32_fwd if cs.fp32_fwd is not None else cs.plan_fwd
-                    cs.fp32_fwd = own if conv_math_of(vals[k]) == 'bf16x3' else None
-                    cs.plan_fwd = vals[k]
-                    self._size_layer(cs)
+                self.set_code(cs, 'fwd', vals[k], self._own_code(cs, 'fwd'))
             else:
-                if vals[k] != cs.plan_dgrad:
-                    own = cs.fp32_dgrad if cs.fp32_dgrad is not None else cs.plan_dgrad
-                    cs.fp32_dgrad = own if conv_math_of(vals[k]) == 'bf16x3' else None
-                cs.plan_dgrad = vals[k]
-                w = vals[len(order) + k]
-                if w != cs.wgrad_wino:
-                    cs.wgrad_wino = w
-                    if w:
-                        cs.wino_ws_floats = self._wino_ws_query(cs, w)
-                    cs.wino_ws = None
-        if stage == 0:
-            self._fit_workspace()
-        if self.conv_math['mode'] != 'fp32':
-            self._conv_math_record()
-        self._det_record()
+                self.set_code(cs, 'dgrad', vals[k], self._own_code(cs, 'dgrad'))
+                self.set_code(cs, 'wgrad', vals[len(order) + k])
+        self._settle()
 
     def _fit_workspace(self):
         need = max([1] + [cs.ws_fwd for cs in self.convs.values()] + [cs.ws_dgrad for cs in self.convs.values()])
@@ -1045,9 +1060,7 @@ class Plan(object):
             return
         self._dgrad_tuned = tune
         self._dgrad_fallback = True
-        for cs in self.convs.values():       # (bf16x3 mode: the choices below start from the fp32 codes)
-            if cs.fp32_dgrad is not None:
-                cs.plan_dgrad, cs.fp32_dgrad = cs.fp32_dgrad, None
+        self._conv_math_revert('dgrad')      # (bf16x3 mode: the choices below start from the fp32 codes)
         if self._tune and tune:
             tune_convs(self, 'dgrad')
             tune_wgrad(self)
@@ -1060,9 +1073,8 @@ class Plan(object):
                 # (the code that was verified, not just the key: a cached Winograd code that SSP_WINOGRAD=0 kept out of
                 # this process must not come back through this fallback)
                 code = _TUNE_CACHE.get(key, 0)
-                cs.plan_dgrad = code if _TUNE_VERIFIED.get(key) == code and form_allowed(kn, wino_tile(code), wino_fused(code)) else 0
-                cs.wgrad_wino = 0
-                cs.fp32_dgrad = None
+                self.set_code(cs, 'dgrad', code if _TUNE_VERIFIED.get(key) == code and form_allowed(kn, wino_tile(code), wino_fused(code)) else 0)
+                self.set_code(cs, 'wgrad', 0)
                 xkey = x3_key(key)
                 xcode = _TUNE_CACHE.get(xkey, 0)
                 cs.x3_dgrad = xcode if xcode and _TUNE_VERIFIED.get(xkey) == xcode else 0
@@ -1073,16 +1085,7 @@ class Plan(object):
         self._conv_math_dgrad()              # bf16x3 mode: the direct data-gradient launches the kernel fits
         if tune:
             self._sync_codes(1)              # multi-GPU: ... and rank 0's data- / filter-gradient choices
-        self._dgrad_sizes()
-
-    def _dgrad_sizes(self):
-        """What follows from the data-gradient plan codes: split-K workspace, BatchNorm-backward fusion buffers."""
-        for cs in self.convs.values():
-            cs.ws_dgrad = 0 if (cs.first or cs.stride == 2) else _lib.query(
-                'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
-        self._plan_bn_fusion()
-        self._fit_workspace()
-        self._det_record()
+        self._settle(dgrad=True)
 
     def _adjoint_rule(self, cs):
         """Whether the layer takes the adjoint form of the data gradient (see _SHARE_DM): its data-gradient plan is a

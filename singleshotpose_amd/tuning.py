@@ -453,25 +453,25 @@ def _scratch(plan, kn, elig, which):
 def _tune_fwd(plan, kn, sc, cs, probe, direct, wino):
     key = fwd_key(plan, cs)
     code = pick(kn, key, probe, direct, wino)
-    cs.plan_fwd = admit(kn, sc.gen, code, key, probe)
+    chosen = admit(kn, sc.gen, code, key, probe)
     # The fastest code of every OTHER family that was timed (direct / F(2x2) / F(4x4)), verified the same way: what the error
     # budget of the forward plans may fall back to (_apply_head_budget); a refused one is dropped.
     fams = _TUNE_FAMILY.get(key) or {}
     cs.fwd_fams = {}
     for f, (c, ms) in fams.items():
-        if c == cs.plan_fwd or (c != code and admit(kn, sc.gen, c, key, probe, primary=False) == c):
+        if c == chosen or (c != code and admit(kn, sc.gen, c, key, probe, primary=False) == c):
             cs.fwd_fams[f] = (c, ms)
     # (a direct family whose tuned code was refused still has the heuristic plan, code 0: the budget can always go direct)
     if 0 not in cs.fwd_fams and 0 in fams:
         cs.fwd_fams[0] = (0, fams[0][1])
-    # not chosen: the transformed-filter buffers go back to the allocator
-    cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
+    plan.set_code(cs, 'fwd', chosen)      # (after fwd_fams: the layer's statistics buffer is sized for every family)
+    plan._release_filters('fwd', [cs])    # not chosen: the transformed-filter buffers go back to the allocator
 
 
 def _tune_dgrad(plan, kn, sc, cs, probe, direct, wino):
     key = plan._dgrad_key(cs)
-    cs.plan_dgrad = admit(kn, sc.gen, pick(kn, key, probe, direct, wino), key, probe)
-    cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
+    plan.set_code(cs, 'dgrad', admit(kn, sc.gen, pick(kn, key, probe, direct, wino), key, probe))
+    plan._release_filters('dgrad', [cs])
 
 
 def x3_launch(plan, cs, which):
@@ -555,11 +555,8 @@ def tune_convs(plan, which):
     for cs in elig if plan.conv_math['mode'] == 'bf16x3-wino' else ():
         setattr(cs, 'x3w_' + which, {t: _tune_x3_wino(plan, kn, sc, cs, probes[cs.ind], key, code)
                                      for t, key, code in x3_wino_launches(plan, cs, which)})
-        # (the forward's transformed filters of a family the layer is not on go back to the allocator, as after the fp32 pass)
-        if which == 'fwd':
-            cs.wino_u = {t: b for t, b in (cs.wino_u or {}).items() if t == wino_tile(cs.plan_fwd)}
-        else:
-            cs.wino_ud = {t: b for t, b in (cs.wino_ud or {}).items() if t == wino_tile(cs.plan_dgrad)}
+        # (the transformed filters of a family the layer is not on go back to the allocator, as after the fp32 pass)
+        plan._release_filters(which, [cs])
     _finish_pass(n_known)
 
 
@@ -620,9 +617,9 @@ def tune_wgrad(plan):
     n_known = len(_TUNE_CACHE)
     det = bool(getattr(plan, 'deterministic', None) and plan.deterministic['mode'])
     for cs in plan.convs.values():
-        cs.wgrad_wino = 0
         forms = wgrad_candidates(kn, cs, plan.B, det)
         if not forms:
+            plan.set_code(cs, 'wgrad', 0)
             continue
         key = plan._wgrad_key(cs)
         if det:      # ordered candidates, ordered kernels, keys of their own: the two modes' caches never mix
@@ -633,9 +630,8 @@ def tune_wgrad(plan):
             wsn = {t: _lib.query('ssp_conv_wgrad_wino_workspace_floats_t', plan.B, cs.H, cs.W, cs.cinp, cs.cout, t) for t in forms}
         cached = _TUNE_CACHE.get(key)
         if cached is not None and (cached == 0 or (cached in forms and (not kn.verify or _TUNE_VERIFIED.get(key) == cached))):
-            cs.wgrad_wino = cached
+            form = cached
         else:
-            cs.wgrad_wino = _TUNE_CACHE[key] = _TUNE_VERIFIED[key] = _time_wgrad(plan, kn, cs, key, forms, max(wsn.values()), gen, det)
-        if cs.wgrad_wino:
-            cs.wino_ws_floats = wsn[cs.wgrad_wino]
+            form = _TUNE_CACHE[key] = _TUNE_VERIFIED[key] = _time_wgrad(plan, kn, cs, key, forms, max(wsn.values()), gen, det)
+        plan.set_code(cs, 'wgrad', form)       # (sizes the layer's workspace for the form: wsn[form])
     _finish_pass(n_known)

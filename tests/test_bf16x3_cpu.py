@@ -240,17 +240,12 @@ def _worker_sync_refused(rank, world, port, q, both_on):
     fn = sync_plans(model)
     assert fn is not None and hasattr(fn, 'all_ok')
     plan = engine.Plan(model, 4, 160, 160, torch.device('cpu'))
-    for cs in plan.convs.values():
-        cs.plan_dgrad, cs.wgrad_wino = 0, 0
     if rank == 0:
-        plan.convs[13].plan_fwd = 12813
-        plan.convs[4].fp32_fwd, plan.convs[4].plan_fwd = 0, X.plan_code(128)
-        plan.convs[8].fp32_dgrad, plan.convs[8].plan_dgrad = 0, X.plan_code(64)
-        for i in (4, 13):
-            plan._size_layer(plan.convs[i])
+        plan.set_code(plan.convs[13], 'fwd', 12813)
+        plan.set_code(plan.convs[4], 'fwd', X.plan_code(128), 0)
+        plan.set_code(plan.convs[8], 'dgrad', X.plan_code(64), 0)
     else:
-        plan.convs[13].plan_fwd = 6414
-        plan._size_layer(plan.convs[13])
+        plan.set_code(plan.convs[13], 'fwd', 6414)
     plan._sync_codes(0)
     plan._sync_codes(1)
     q.put((rank, {i: (cs.plan_fwd, cs.plan_dgrad, cs.fp32_fwd, cs.fp32_dgrad, cs.tile_m, cs.ntile) for i, cs in plan.convs.items()},

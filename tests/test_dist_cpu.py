@@ -261,17 +261,14 @@ def _worker_plan_sync(rank, world, port, q):
     model = Darknet(os.path.join(ROOT, 'cfg', 'yolo-pose.cfg'))
     assert sync_plans(model) is not None
     plan = engine.Plan(model, 4, 160, 160, torch.device('cpu'))
-    for cs in plan.convs.values():
-        cs.plan_dgrad, cs.wgrad_wino = 0, 0
     before = {i: (cs.tile_m, cs.ntile, cs.ws_fwd, cs.stats.numel() if cs.bn else 0) for i, cs in plan.convs.items()}
     if rank == 0:
-        plan.convs[8].plan_fwd = 8006413            # F(4x4), 64-row GEMM tiles
-        plan.convs[12].plan_fwd = 9006413           # F(2x2)
-        plan.convs[13].plan_fwd = 12813             # a direct tile choice
-        plan.convs[8].plan_dgrad, plan.convs[8].wgrad_wino = 8006413, 4
-        plan.convs[18].plan_dgrad, plan.convs[18].wgrad_wino = 6413, 2
-        for i in (8, 12, 13):
-            plan._size_layer(plan.convs[i])
+        plan.set_code(plan.convs[8], 'fwd', 8006413)            # F(4x4), 64-row GEMM tiles
+        plan.set_code(plan.convs[12], 'fwd', 9006413)           # F(2x2)
+        plan.set_code(plan.convs[13], 'fwd', 12813)             # a direct tile choice
+        for i, code, form in ((8, 8006413, 4), (18, 6413, 2)):
+            plan.set_code(plan.convs[i], 'dgrad', code)
+            plan.set_code(plan.convs[i], 'wgrad', form)
         plan.convs[8].wino_ws_floats = 123
     plan._sync_codes(0)
     plan._sync_codes(1)
@@ -322,26 +319,20 @@ def _worker_plan_sync_refused(rank, world, port, q):
     fn = sync_plans(model)
     assert fn is not None and hasattr(fn, 'all_ok')
     plan = engine.Plan(model, 4, 160, 160, torch.device('cpu'))
-    for cs in plan.convs.values():
-        cs.plan_dgrad, cs.wgrad_wino = 0, 0
     if rank == 0:
-        plan.convs[8].plan_fwd = 8006413
-        plan.convs[4].plan_fwd = engine.WINOF
-        plan.convs[13].plan_fwd = 12813
-        plan.convs[8].plan_dgrad, plan.convs[8].wgrad_wino = engine.WINOF, engine.WGRAD_FUSED
-        for i in (4, 8, 13):
-            plan._size_layer(plan.convs[i])
+        plan.set_code(plan.convs[8], 'fwd', 8006413)
+        plan.set_code(plan.convs[4], 'fwd', engine.WINOF)
+        plan.set_code(plan.convs[13], 'fwd', 12813)
+        plan.set_code(plan.convs[8], 'dgrad', engine.WINOF)
+        plan.set_code(plan.convs[8], 'wgrad', engine.WGRAD_FUSED)
     else:
-        plan.convs[13].plan_fwd = 6414      # this rank's own (direct) choice is dropped as well: same plans everywhere
-        plan._size_layer(plan.convs[13])
+        plan.set_code(plan.convs[13], 'fwd', 6414)      # this rank's own (direct) choice is dropped as well: same plans everywhere
     plan._sync_codes(0)
     plan._sync_codes(1)
     # a message of another SHAPE (rank 1's plan is for another input size) must neither hang nor be adopted
     other = engine.Plan(model, 4, 160 if rank == 0 else 192, 160, torch.device('cpu'))
-    for cs in other.convs.values():
-        cs.plan_dgrad, cs.wgrad_wino = 0, 0
     if rank == 0:
-        other.convs[13].plan_fwd = 12813
+        other.set_code(other.convs[13], 'fwd', 12813)
     other._sync_codes(0)
     q.put((rank, {i: (cs.plan_fwd, cs.plan_dgrad, cs.wgrad_wino) for i, cs in plan.convs.items()},
            {i: cs.plan_fwd for i, cs in other.convs.items()}))

@@ -47,24 +47,16 @@ def _snapshot(side):
 def _copy_codes(src, dst):
     """The twin's plan runs the kernels the model's plan runs (the tuned variant): forward codes as _apply_head_budget moves a
     layer, data- / filter-gradient choices as _sync_codes adopts them."""
-    from singleshotpose_amd import _lib
     for ind, cs in src.convs.items():
-        d = dst.convs[ind]
-        d.plan_fwd = cs.plan_fwd
-        dst._size_layer(d)
-    dst._fit_workspace()
+        dst.set_code(dst.convs[ind], 'fwd', cs.plan_fwd)
+    dst._settle()
     dst._head_budget_done = True
     if src._dgrad_tuned:
         dst._prepare_backward()
         for ind, cs in src.convs.items():
-            d = dst.convs[ind]
-            d.plan_dgrad = cs.plan_dgrad
-            if d.wgrad_wino != cs.wgrad_wino:
-                d.wgrad_wino, d.wino_ws_floats, d.wino_ws = cs.wgrad_wino, cs.wino_ws_floats, None
-            d.ws_dgrad = 0 if d.first else _lib.query('ssp_conv_workspace_floats', dst.B, d.H, d.W, d.coutp, d.cin, d.k,
-                                                      d.plan_dgrad)
-        dst._plan_bn_fusion()
-        dst._fit_workspace()
+            dst.set_code(dst.convs[ind], 'dgrad', cs.plan_dgrad)
+            dst.set_code(dst.convs[ind], 'wgrad', cs.wgrad_wino)
+        dst._settle()
 
 
 def _twin_run(side, snap, o, pos, monkeypatch, tuned):
@@ -274,9 +266,8 @@ def test_sequence_on_tuned_plans(seq, monkeypatch, tmp_path):
     forced = not engine.wino_tile(cs.plan_fwd)
     if forced:
         assert cs.k == 3 and cs.cin % 16 == 0 and cs.cout % 16 == 0 and cs.cinp == cs.cin and not cs.first
-        cs.plan_fwd = WINO2
-        plan._size_layer(cs)
-        plan._fit_workspace()
+        plan.set_code(cs, 'fwd', WINO2)
+        plan._settle()
     plan._head_budget_done = True
     print('SEQ %s Winograd forward layers chosen by the tuner: %s; layer %d: %s' % (
         seq.id, chosen, cs.ind, 'WINO2 set by the test' if forced else 'the tuner\'s code %d' % cs.plan_fwd))
@@ -284,3 +275,37 @@ def test_sequence_on_tuned_plans(seq, monkeypatch, tmp_path):
     print('SEQ %s codes %s' % (seq.id, [(c.ind, c.plan_fwd, c.plan_dgrad, c.wgrad_wino) for c in plan.convs.values()]))
     assert engine.wino_tile(cs.plan_fwd)
     assert cs.ind in plan.wino_version or any(o.kind == 'eval_graph' for o in seq.ops), "no Winograd-transformed filter was cached"
+
+
+def test_a_moved_forward_code_recaptures_the_inference_graph(monkeypatch):
+    """A captured inference chain holds the plan codes and the transformed-filter pointers of its moment: after conv ordinal
+    2 moves from F(4x4) to F(2x2) and the F(4x4) filters are released - what the end of _apply_head_budget does - the next
+    graph forward captures again and equals the eager forward bit for bit."""
+    from exact_conv import WINO2, WINO4
+    monkeypatch.setenv('SSP_AUTOTUNE', '1')
+    monkeypatch.delenv('SSP_TUNE_CACHE', raising=False)
+    model = S.build_model(TUNED_NET).cuda().eval()
+    plan = model._plan(TUNED_NET.shapes['A'], torch.device('cuda', torch.cuda.current_device()))
+    cs = plan.convs[sorted(plan.convs)[TUNED_NET.mid]]
+    assert cs.k == 3 and cs.cin == cs.cout == 64 and cs.stride == 1 and not cs.first
+    plan.set_code(cs, 'fwd', WINO4)
+    plan._settle()
+    x = T.make_input(TUNED_CASE, 0).cuda()
+    with torch.no_grad():
+        model.graph_inference = True
+        model(x)
+        graph0 = plan._graph
+        model(x)
+        assert graph0 is not None and plan._graph is graph0 and not plan._graph_failed
+        u4 = id(cs.wino_u[4])
+        plan.set_code(cs, 'fwd', WINO2)
+        plan._settle()
+        plan._release_filters('fwd', [cs])
+        assert 4 not in cs.wino_u
+        y = model(x)
+        assert plan._graph is not graph0 and plan._graph is not None
+        model.graph_inference = False
+        want = model(x)
+    print('SEQ recapture: F(4x4) filters %#x released, F(2x2) filters %#x, distance to the eager forward %.2e' % (
+        u4, id(cs.wino_u[2]), _dist(y, want)))
+    assert torch.equal(y, want)

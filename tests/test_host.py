@@ -502,3 +502,96 @@ def test_plan_code_families():
     assert engine.wino_tile(engine.WINOF) == 2 and engine.wino_fused(engine.WINOF)
     assert not engine.wino_fused(9006413) and not engine.wino_fused(8006413) and not engine.wino_fused(0)
     assert engine.WGRAD_FUSED == 12
+
+
+# ------------------------------------------------------------------------------------------------ plan codes: writer and settle
+def _cpu_plan(monkeypatch, model=None, shape=(4, 160, 160)):
+    """A plan on CPU buffers (host queries only, no launch) with a stand-in for a captured graph and a shared workspace
+    that no code of these tests outgrows."""
+    from singleshotpose_amd import engine
+    from singleshotpose_amd.darknet import Darknet
+    monkeypatch.setenv('SSP_AUTOTUNE', '0')
+    plan = engine.Plan(model or Darknet(os.path.join(ROOT, 'cfg', 'yolo-pose.cfg')), *shape, torch.device('cpu'))
+    plan.ws_floats = 1 << 40
+    plan._graph = sentinel = object()
+    return plan, sentinel
+
+
+def test_head_budget_stale_drops_the_captured_graph(monkeypatch):
+    plan, _ = _cpu_plan(monkeypatch)
+    cs = plan.convs[8]
+    plan.set_code(cs, 'fwd', 12813)
+    plan._settle()
+    cs.fwd_fams = {0: (12813, 1.0), 4: (8006413, 0.5)}
+    plan._graph = object()
+    plan._head_budget_done = True
+    plan.head_budget_stale()
+    assert cs.plan_fwd == 8006413 and cs.tile_m == 0 and plan._graph is None
+
+
+def test_sync_codes_drops_the_captured_graph_only_when_a_forward_code_changes(monkeypatch):
+    plan, sentinel = _cpu_plan(monkeypatch)
+    plan.net._plan_sync = lambda msg: list(msg)                      # every rank already runs rank 0's codes
+    plan._sync_codes(0)
+    assert plan._graph is sentinel
+    k = 5 + sorted(plan.convs).index(8)
+    plan.net._plan_sync = lambda msg: msg[:k] + [9006413] + msg[k + 1:]
+    plan._sync_codes(0)
+    assert plan.convs[8].plan_fwd == 9006413 and plan._graph is None
+
+
+def test_writer_settle_and_release_leave_one_filter_family_and_no_graph(monkeypatch):
+    plan, sentinel = _cpu_plan(monkeypatch)
+    cs = plan.convs[8]
+    plan.set_code(cs, 'fwd', 8006413)
+    plan._settle()
+    plan._wino_u(cs, 4)
+    plan._graph = sentinel
+    plan._settle()                       # nothing was written since: the graph stays
+    assert plan._graph is sentinel
+    plan.set_code(cs, 'fwd', 9006413)
+    plan._wino_u(cs, 2)
+    assert sorted(cs.wino_u) == [2, 4]   # (the writer releases nothing: the head budget's forwards re-use the buffers)
+    plan._settle()
+    plan._release_filters('fwd', [cs])
+    assert sorted(cs.wino_u) == [2] and plan._graph is None
+    # a released buffer alone drops the graph as well
+    plan._wino_u(cs, 4)
+    plan._graph = sentinel
+    plan._release_filters('fwd', [cs])
+    plan._settle()
+    assert sorted(cs.wino_u) == [2] and plan._graph is None
+
+
+def test_writer_keeps_the_fp32_code_of_a_substituted_launch_only(monkeypatch):
+    from singleshotpose_amd import engine
+    plan, sentinel = _cpu_plan(monkeypatch)
+    cs = plan.convs[8]
+    plan.set_code(cs, 'dgrad', 12813, 6413)                          # an fp32 code needs none to go back to
+    assert (cs.plan_dgrad, cs.fp32_dgrad) == (12813, None)
+    plan.set_code(cs, 'dgrad', engine.BF16X3 + 12813, 12813)
+    assert (cs.plan_dgrad, cs.fp32_dgrad) == (engine.BF16X3 + 12813, 12813)
+    plan._settle()
+    assert plan._graph is sentinel                                    # (data-gradient codes are not part of the graph)
+    assert plan.conv_math['layers'] == {8: (0, engine.BF16X3 + 12813)}
+    plan._conv_math_revert('dgrad')
+    assert (cs.plan_dgrad, cs.fp32_dgrad) == (12813, None) and plan.conv_math['layers'] == {}
+    plan.set_code(cs, 'wgrad', 4)
+    assert cs.wino_ws_floats == plan._wino_ws_query(cs, 4) and cs.wino_ws is None
+
+
+def test_a_stride2_block_keeps_no_data_gradient_workspace_after_a_settle(monkeypatch):
+    import sequence_cases as S
+    net = S.STRIDED_NET
+    plan, _ = _cpu_plan(monkeypatch, S.build_model(net), net.shapes['A'])
+    strided = [cs for cs in plan.convs.values() if cs.stride == 2]
+    assert strided and not any(cs.first for cs in strided)
+    plan._settle(dgrad=True)
+    assert all(cs.ws_dgrad == 0 for cs in strided)
+    later = [cs for cs in plan.convs.values() if cs.stride == 1 and not cs.first and cs.k == 3 and cs.cinp % 16 == 0]
+    from singleshotpose_amd import _lib
+    cs = later[0]
+    plan.set_code(cs, 'dgrad', 12893)                                 # a write: every block is re-sized with it
+    plan._settle()
+    assert cs.ws_dgrad == _lib.query('ssp_conv_workspace_floats', plan.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, 12893)
+    assert all(cs.ws_dgrad == 0 for cs in strided)

@@ -198,14 +198,10 @@ def _worker(rank, world, port, q, rank1_mode):
     fn = sync_plans(model)
     assert fn is not None and hasattr(fn, 'all_ok')
     plan = engine.Plan(model, 4, 160, 160, torch.device('cpu'))
-    for cs in plan.convs.values():
-        cs.plan_dgrad, cs.wgrad_wino = 0, 0
     if rank == 0:
-        plan.convs[13].plan_fwd = 12813
-        plan.convs[4].fp32_fwd, plan.convs[4].plan_fwd = 8012813, 8612813
-        plan.convs[8].fp32_dgrad, plan.convs[8].plan_dgrad = 9006413, 9606413
-        for i in (4, 13):
-            plan._size_layer(plan.convs[i])
+        plan.set_code(plan.convs[13], 'fwd', 12813)
+        plan.set_code(plan.convs[4], 'fwd', 8612813, 8012813)
+        plan.set_code(plan.convs[8], 'dgrad', 9606413, 9006413)
     plan._sync_codes(0)
     plan._sync_codes(1)
     q.put((rank, {i: (cs.plan_fwd, cs.plan_dgrad, cs.fp32_fwd, cs.fp32_dgrad) for i, cs in plan.convs.items()},

@@ -73,12 +73,9 @@ def force_wgrad_wino(plan, tile):
     for cs in plan.convs.values():
         ok = (cs.k == 3 and cs.stride == 1 and not cs.first and cs.cinp == cs.cin and cs.coutp == cs.cout and
               _lib.query('ssp_conv_wgrad_wino_ordered_split', plan.B, cs.H, cs.W, cs.cinp, cs.cout, tile, 0) > 0)
-        cs.wgrad_wino = tile if ok else 0
-        cs.wino_ws = None
-        if ok:
-            cs.wino_ws_floats = plan._wino_ws_query(cs, tile)
-            n += 1
-    plan._dgrad_sizes()
+        plan.set_code(cs, 'wgrad', tile if ok else 0)
+        n += ok
+    plan._settle(dgrad=True)
     return n
 
 
