@@ -482,6 +482,16 @@ int ssp_avgpool_bwd(const float* g, int ldg, float* dx, int lddx, int C, int B, 
 int ssp_softmax_fwd(const float* x, int ldx, float* y, int ldy, int C, int64_t M, void* stream);
 int ssp_softmax_bwd(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M, int accumulate,
                     void* stream);
+/* [upsample] stride=N (csrc/upsample.hip; appended to ABI 5): nearest-neighbour replication, dst[b,y,x,c] =
+ * src[b,y/N,x/N,c] - F.interpolate(scale_factor=N, mode='nearest').  H x W is the SOURCE (coarse) map in both calls;
+ * C % 4 == 0 (the padded count of a padded map); every stride a multiple of 4 and >= C; pointers 16-byte aligned;
+ * 1 <= stride <= 8; B * H * W * stride^2 < 2^31 - anything else is SSP_ERR_ARG and nothing is launched.  Only columns
+ * [0, C) of a row are read or written, so either side may be a channel slice of a wider buffer.
+ * Backward: dsrc[b,y,x,c] (=|+=) sum of the N x N window of g, taken row-major with sequential fp32 adds (s = g00;
+ * s += g01; ...), then dsrc = accumulate ? dsrc + s : s; one thread per element, no atomics: the same bits every run */
+int ssp_upsample_fwd(const float* src, int lds, float* dst, int ldd, int C, int B, int H, int W, int stride, void* stream);
+int ssp_upsample_bwd(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride,
+                     int accumulate, void* stream);
 
 /* ---- RegionLoss (region_loss.py:9-175, region_loss_multi.py:9-189, utils.py:138-187) ----------------------- */
 /* out, grad: (nB, nA*(2K+1+nC), nH, nW) NCHW contiguous; target: (nB, 50*(2K+3)) float or double on the device;

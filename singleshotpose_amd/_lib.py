@@ -104,6 +104,8 @@ _SIGS = {
     "ssp_avgpool_bwd": [P, I, P, I, I, I, I, I, I, P],
     "ssp_softmax_fwd": [P, I, P, I, I, L, P],
     "ssp_softmax_bwd": [P, I, P, I, P, I, I, L, I, P],
+    "ssp_upsample_fwd": [P, I, P, I, I, I, I, I, I, P],
+    "ssp_upsample_bwd": [P, I, P, I, I, I, I, I, I, I, P],
     "ssp_region_loss": [P, P, I, P, P, P, I, I, I, I, I, I, F, F, F, F, F, I, I, P, I, P],
     "ssp_region_decode_argmax": [P, P, I, I, I, I, I, I, I, P],
     "ssp_region_decode_all": [P, P, I, I, I, I, I, I, P],

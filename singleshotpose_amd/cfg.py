@@ -8,6 +8,7 @@ File formats:
   .cfg      "[section]" starts a block, "key=value" lines (both sides stripped), '#' comments; every value stays a
             string; a key literally called "type" is stored as "_type"; convolutional blocks default
             batch_normalize to 0.
+            an [upsample] block (nearest-neighbour replication by stride=N, default 2) has no parameters.
   .weights  float32 stream; per conv block with BN: bn.bias, bn.weight, running_mean, running_var, conv.weight;
             without BN: conv.bias, conv.weight; conv.weight flattened in (Cout, Cin, kh, kw) order.
 """
@@ -44,6 +45,16 @@ def resolve_layers(spec, ind):
     return [int(i) if int(i) > 0 else int(i) + ind for i in spec.split(',')]
 
 
+def upsample_stride(block, ind):
+    """stride of an [upsample] block (Darknet's default is 2).  Its output is nearest-neighbour replication, out[y][x] =
+    in[y // stride][x // stride]; Darknet's `scale=` multiplies the values on top of that, which no kernel here does, so
+    any value but 1 is refused."""
+    if float(block.get('scale', 1)) != 1.0:
+        raise NotImplementedError("block %d (upsample): scale=%s (only scale=1, plain nearest-neighbour replication, is built)"
+                                  % (ind, block['scale']))
+    return int(block.get('stride', 2))
+
+
 def layer_shapes(blocks, width=None, height=None):
     """(width, height, filters) of every layer's output, index-aligned with Darknet.models (block 0 excluded).
 
@@ -70,6 +81,9 @@ def layer_shapes(blocks, width=None, height=None):
         elif t == 'reorg':
             s = int(block['stride'])
             w, h, c = w // s, h // s, c * s * s
+        elif t == 'upsample':
+            s = upsample_stride(block, ind)
+            w, h = w * s, h * s
         elif t == 'route':
             layers = resolve_layers(block['layers'], ind)
             w, h = out[layers[0]][0], out[layers[0]][1]
@@ -107,6 +121,8 @@ def print_cfg(blocks):
             print('%5d %-6s                                     ->  %3d' % (ind, 'cost', pc))
         elif t == 'reorg':
             print('%5d %-6s             / %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (ind, 'reorg', int(block['stride']), pw, ph, pc, w, h, c))
+        elif t == 'upsample':
+            print('%5d %-8s           * %d   %3d x %3d x%4d   ->   %3d x %3d x%4d' % (ind, 'upsample', upsample_stride(block, ind), pw, ph, pc, w, h, c))
         elif t == 'route':
             layers = resolve_layers(block['layers'], ind)
             print(('%5d %-6s' + ' %d' * len(layers)) % ((ind, 'route') + tuple(layers)))

@@ -122,6 +122,10 @@ int ssp_avgpool_bwd_launch(const float* g, int ldg, float* dx, int lddx, int C, 
 int ssp_softmax_fwd_launch(const float* x, int ldx, float* y, int ldy, int C, int64_t M, hipStream_t stream);
 int ssp_softmax_bwd_launch(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M,
                            int accumulate, hipStream_t stream);
+int ssp_upsample_fwd_launch(const float* src, int lds_, float* dst, int ldd, int C, int B, int H, int W, int stride,
+                            hipStream_t stream);
+int ssp_upsample_bwd_launch(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride,
+                            int accumulate, hipStream_t stream);
 int ssp_region_loss_launch(const float* out, const void* target, int target_is_f64, float* grad, float* partials,
                            float* stats, int nB, int nA, int nC, int nH, int nW, int num_keypoints,
                            float noobject_scale, float object_scale, float coord_scale, float class_scale, float thresh,
@@ -597,6 +601,13 @@ int ssp_softmax_fwd(const float* x, int ldx, float* y, int ldy, int C, int64_t M
 int ssp_softmax_bwd(const float* y, int ldy, const float* g, int ldg, float* dx, int lddx, int C, int64_t M, int accumulate,
                     void* stream) {
   return ssp_softmax_bwd_launch(y, ldy, g, ldg, dx, lddx, C, M, accumulate, (hipStream_t)stream);
+}
+int ssp_upsample_fwd(const float* src, int lds, float* dst, int ldd, int C, int B, int H, int W, int stride, void* stream) {
+  return ssp_upsample_fwd_launch(src, lds, dst, ldd, C, B, H, W, stride, (hipStream_t)stream);
+}
+int ssp_upsample_bwd(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride, int accumulate,
+                     void* stream) {
+  return ssp_upsample_bwd_launch(g, ldg, dsrc, ldds, C, B, H, W, stride, accumulate, (hipStream_t)stream);
 }
 
 int ssp_region_loss(const float* out, const void* target, int target_is_f64, float* grad, float* partials,

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cfg import (load_conv, load_conv_bn, load_fc, parse_cfg, print_cfg, resolve_layers, save_conv, save_conv_bn,
-                  save_fc)
+                  save_fc, upsample_stride)
 from .engine import Plan, _DarknetEvalFn, _DarknetFn, weights_changed
 from .region_loss import RegionLoss, RegionLossMulti
 
@@ -39,6 +39,14 @@ class MaxPoolStride1(_HipOnly):
 class Reorg(_HipOnly):
     def __init__(self, stride=2):
         super(Reorg, self).__init__()
+        self.stride = stride
+
+
+class Upsample(_HipOnly):
+    """[upsample]: nearest-neighbour replication by `stride` (engine.Plan's 'upsample' op, csrc/upsample.hip)."""
+
+    def __init__(self, stride=2):
+        super(Upsample, self).__init__()
         self.stride = stride
 
 
@@ -150,6 +158,10 @@ class Darknet(nn.Module):
                 prev_filters = stride * stride * prev_filters
                 out_filters.append(prev_filters)
                 models.append(Reorg(stride))
+            elif t == 'upsample':
+                # no parameters (the .weights readers and writers pass it by); the channel count is the source's
+                models.append(Upsample(upsample_stride(block, len(models))))
+                out_filters.append(prev_filters)
             elif t == 'route':
                 ind = len(models)
                 layers = resolve_layers(block['layers'], ind)
@@ -197,7 +209,10 @@ class Darknet(nn.Module):
                 out_filters.append(prev_filters)
                 models.append(loss)
             else:
+                # (an entry all the same: the indices of the later blocks - state_dict keys, route targets - stay aligned)
                 print('unknown type %s' % t)
+                out_filters.append(prev_filters)
+                models.append(EmptyModule())
         return models
 
     @property

@@ -9,6 +9,8 @@ Forward per conv block (darknet.py:145-167):
     -> ssp_bn_fwd_finalize (train) | ssp_bn_eval_prepare (eval) -> ssp_bn_act_fwd (BN + leaky [+ fused 2x2 max-pool])
 A max-pool block is fused into the preceding conv block when nothing else consumes the un-pooled map.
 route = alias or ssp_copy_channels into a concat buffer; reorg = ssp_reorg.
+upsample = ssp_upsample_fwd / ssp_upsample_bwd (csrc/upsample.hip): nearest-neighbour replication, written straight into the
+concatenation buffer of the two-layer route behind it when that route is its only consumer (Plan.upsample).
 The other Darknet blocks (darknet.py:8-47, :107-118, :168-229) run on csrc/generic_blocks.hip: stride-1 max-pool, shortcut,
 global average pool, softmax over channels; a connected block is planned as a 1x1 convolution of its (B, Cin) input on a 1x1
 map (M = B rows: the conv kernels, bias and activation path of a non-BN conv block).
@@ -27,7 +29,7 @@ import weakref
 import torch
 
 from . import _lib
-from .cfg import layer_shapes, resolve_layers
+from .cfg import layer_shapes, resolve_layers, upsample_stride
 
 from .tuning import (BF16X3, BN_EPS, BN_MOMENTUM, CONV_MATHS, IGEMM_CANDS, IGEMM_LATENCY_CANDS, TUNE_REJECTED,  # noqa: F401
                      WGRAD_FUSED, WINO, WINO4, WINO_GEMM_CANDS, WINOF, _HEAD_BUDGET_CACHE, _HEAD_BUDGET_PINNED, _TUNE_CACHE,
@@ -167,12 +169,14 @@ OpSchedule = collections.namedtuple('OpSchedule', 'ind kind visited dgrad wgrad 
 
 class _Op(object):
     """One executed block other than a conv / connected block (those are _ConvSpec records): its kind ('maxpool',
-    'maxpool_s1', 'reorg', 'shortcut', 'avgpool', 'softmax', 'alias' = one-layer route, 'concat'), layer index, input maps,
-    output map and, for a shortcut, the activation's slope."""
-    __slots__ = ('kind', 'ind', 'srcs', 'out', 'slope')
+    'maxpool_s1', 'reorg', 'upsample', 'shortcut', 'avgpool', 'softmax', 'alias' = one-layer route or stride-1 upsample,
+    'concat'), layer index, input maps, output map and, for a shortcut, the activation's slope; for an upsample `stride`; for
+    a concat `inplace` = its first source is an upsample that writes its columns of the buffer itself (Plan.upsample)."""
+    __slots__ = ('kind', 'ind', 'srcs', 'out', 'slope', 'stride', 'inplace')
 
-    def __init__(self, kind, ind, srcs, out, slope=None):
+    def __init__(self, kind, ind, srcs, out, slope=None, stride=None):
         self.kind, self.ind, self.srcs, self.out, self.slope = kind, ind, srcs, out, slope
+        self.stride, self.inplace = stride, False
 
     @property
     def oind(self):
@@ -255,7 +259,7 @@ class Plan(object):
         consumers = [[] for _ in range(nl)]
         for ind, block in enumerate(blocks[1:]):
             t = block['type']
-            if t in ('convolutional', 'maxpool', 'reorg', 'avgpool', 'softmax', 'connected'):
+            if t in ('convolutional', 'maxpool', 'reorg', 'upsample', 'avgpool', 'softmax', 'connected'):
                 if ind > 0:
                     consumers[ind - 1].append(ind)
             elif t == 'route':
@@ -289,6 +293,12 @@ class Plan(object):
 
         self.convs = {}      # layer index -> _ConvSpec
         self.fused_pool = set()   # maxpool layers folded into the preceding conv block
+        # the form each upsample block took: 'route' = its output IS columns [0, C) of the concatenation buffer of the
+        # two-layer route behind it (no copy of the fine map in either direction), 'own' = a buffer of its own,
+        # 'alias' = stride 1, nothing to run.  SSP_UPSAMPLE_FUSE=0 (read when the plan is built) forces 'own' (A/B runs)
+        self.upsample = {}
+        up_fuse = os.environ.get('SSP_UPSAMPLE_FUSE', '1') != '0'
+        route_buf = {}            # route layer -> the concatenation buffer its upsample source already writes into
         self.acts = [None] * nl   # forward outputs
         self.ops = []        # one record per executed block (_ConvSpec or _Op), in forward order; backward runs it reversed
         wsz = dsz = 0
@@ -398,6 +408,34 @@ class Plan(object):
                     raise NotImplementedError("block %d (reorg): reorg of a %d x %d map (ssp_reorg needs even H and W)"
                                               % (ind, prev.W, prev.H))
                 op = _Op('reorg', ind, [prev], _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c))
+            elif t == 'upsample':
+                n = upsample_stride(block, ind)       # (refuses scale != 1 by name; layer_shapes above already did)
+                if not 1 <= n <= 8:
+                    raise NotImplementedError("block %d (upsample): stride=%d is outside 1..8 (ssp_upsample_fwd)" % (ind, n))
+                if prev.flat:
+                    raise NotImplementedError("block %d (upsample): its input is a flat (B, %d) map (behind avgpool / "
+                                              "connected); there is no H x W to replicate" % (ind, prev.C))
+                if n == 1:
+                    self.upsample[ind] = 'alias'
+                    op = _Op('alias', ind, [prev], prev)
+                else:
+                    # write-through: the only consumer is the two-layer route right behind it (one block of look-ahead, as
+                    # cs.pool does), both of its sources have whole channel quads and the lateral map has the fine shape
+                    nxt = blocks[ind + 2] if ind + 2 < len(blocks) else None
+                    lat = None
+                    if up_fuse and nxt is not None and nxt['type'] == 'route' and consumers[ind] == [ind + 1]:
+                        layers = resolve_layers(nxt['layers'], ind + 1)
+                        if len(layers) == 2 and layers[0] == ind and 0 <= layers[1] < ind:
+                            lat = self.acts[layers[1]]
+                    if lat is not None and c % 4 == 0 and lat.C % 4 == 0 and (lat.H, lat.W) == (h, w) and not lat.flat:
+                        ct = c + lat.C
+                        buf = route_buf[ind + 1] = torch.empty(B * h * w * ct, **f32)
+                        out = _Act(buf, 0, c, h, w, ct)
+                        self.upsample[ind] = 'route'
+                    else:
+                        out = _Act(zeros_or_empty(B * h * w * _pad4(c), **f32), 0, c, h, w, _pad4(c))
+                        self.upsample[ind] = 'own'
+                    op = _Op('upsample', ind, [prev], out, stride=n)
             elif t == 'shortcut':
                 f = resolve_layers(block['from'], ind)[0]
                 a, b = self.acts[f], prev
@@ -436,7 +474,10 @@ class Plan(object):
                         if s.C % 4:
                             raise NotImplementedError("block %d (route): concatenates layer %d with %d channels "
                                                       "(ssp_copy_channels needs multiples of 4)" % (ind, l, s.C))
-                    op = _Op('concat', ind, srcs, _Act(torch.empty(B * h * w * c, **f32), 0, c, h, w, c, srcs[0].flat))
+                    buf = route_buf.get(ind)
+                    op = _Op('concat', ind, srcs, _Act(torch.empty(B * h * w * c, **f32) if buf is None else buf, 0, c, h, w, c,
+                                                       srcs[0].flat))
+                    op.inplace = buf is not None      # (srcs[0] is columns [0, srcs[0].C) of buf already)
             else:  # region / cost: not executed in forward (darknet.py:119-127)
                 self._place(ind, prev)
                 continue
@@ -982,7 +1023,8 @@ class Plan(object):
 
     @staticmethod
     def _distinct_bytes(ts):
-        """Bytes of the distinct storages among tensors ts (None entries skipped)."""
+        """Bytes of the distinct storages among tensors ts (None entries skipped).  (An upsample written into its route's
+        buffer shares that buffer, and its gradient the route's gradient buffer: footprint() and nbytes_now() count each once.)"""
         seen, total = set(), 0
         for t in ts:
             if t is not None and t.data_ptr() not in seen:
@@ -1319,6 +1361,8 @@ class Plan(object):
                 call('ssp_maxpool_s1_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, st)
             elif kind == 'reorg':
                 call('ssp_reorg', src.ptr, src.ld, out.ptr, out.ld, src.C, B, src.H, src.W, 0, 0, st)
+            elif kind == 'upsample':
+                call('ssp_upsample_fwd', src.ptr, src.ld, out.ptr, out.ld, _pad4(src.C), B, src.H, src.W, op.stride, st)
             elif kind == 'shortcut':
                 a, b = op.srcs
                 call('ssp_shortcut_fwd', a.ptr, a.ld, b.ptr, b.ld, out.ptr, out.ld, _pad4(out.C), B * out.H * out.W, op.slope,
@@ -1329,8 +1373,9 @@ class Plan(object):
                 call('ssp_softmax_fwd', src.ptr, src.ld, out.ptr, out.ld, src.C, B * src.H * src.W, st)
             elif kind == 'concat':
                 off = 0
-                for s in op.srcs:
-                    call('ssp_copy_channels', s.ptr, s.ld, _ptr(out.t, off), out.ld, s.C, B * s.H * s.W, 0, st)
+                for n, s in enumerate(op.srcs):
+                    if not (n == 0 and op.inplace):      # (an upsample wrote its columns of the buffer itself)
+                        call('ssp_copy_channels', s.ptr, s.ld, _ptr(out.t, off), out.ld, s.C, B * s.H * s.W, 0, st)
                     off += s.C
             # ('alias', a one-layer route: its output is the source's map, nothing to run)
 
@@ -1735,8 +1780,13 @@ class Plan(object):
                      _pad4(out.C), B * out.H * out.W, op.slope, st)
             elif kind in ('alias', 'concat'):
                 off = 0
-                for a, d in zip(op.srcs, s.dgrad):
-                    if d:
+                for n, (a, d) in enumerate(zip(op.srcs, s.dgrad)):
+                    if d and n == 0 and kind == 'concat' and op.inplace:
+                        # the upsample's gradient IS columns [0, C) of this buffer: ssp_upsample_bwd reads it in place
+                        # (its only consumer is this route, so nothing else adds to it)
+                        self.grads[a.producer] = _Act(g.t, g.off, a.C, a.H, a.W, g.ld)
+                        written.add(a.producer)
+                    elif d:
                         gin, acc = grad_in(a)
                         call('ssp_copy_channels', _ptr(g.t, g.off + off), g.ld, gin.ptr, gin.ld, a.C, B * a.H * a.W, acc, st)
                     off += a.C
@@ -1748,6 +1798,8 @@ class Plan(object):
                          gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, acc, st)
                 elif kind == 'reorg':
                     call('ssp_reorg', g.ptr, g.ld, gin.ptr, gin.ld, src.C, B, src.H, src.W, 1, acc, st)
+                elif kind == 'upsample':
+                    call('ssp_upsample_bwd', g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, op.stride, acc, st)
                 elif kind == 'avgpool':
                     call('ssp_avgpool_bwd', g.ptr, g.ld, gin.ptr, gin.ld, _pad4(src.C), B, src.H, src.W, acc, st)
                 else:

@@ -23,7 +23,8 @@ def family(code):
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 416
-m = Darknet(os.path.join(ROOT, 'cfg', 'yolo-pose.cfg')).cuda().train()
+CFG = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'cfg', 'yolo-pose.cfg')      # (e.g. cfg/yolo-pose-up.cfg)
+m = Darknet(CFG).cuda().train()
 x = torch.rand(B, 3, S, S, device='cuda')
 m(x).sum().backward()
 plan = list(m._plans.values())[0]
@@ -31,6 +32,10 @@ for ind, cs in sorted(plan.convs.items()):
     print('layer %2d  %4dx%-4d %4d->%-4d k%d  fwd %7d %-14s  dgrad %7d %-14s  wgrad %s' % (
         ind, cs.H, cs.W, cs.cin, cs.cout, cs.k, cs.plan_fwd, family(cs.plan_fwd), cs.plan_dgrad, family(cs.plan_dgrad),
         ('winograd F(%dx%d)' % (cs.wgrad_wino, cs.wgrad_wino)) if getattr(cs, 'wgrad_wino', 0) else 'direct'))
+for ind, form in sorted(plan.upsample.items()):      # 'route': written into the concatenation buffer of the route behind it
+    a = plan.acts[ind]
+    print('layer %2d  upsample x%s -> %dx%d x%d, row stride %d: %s' % (
+        ind, m.blocks[ind + 1].get('stride', 2), a.H, a.W, a.C, a.ld, form))
 print('conv math: %r' % (plan.conv_math,))
 det = plan.deterministic
 print('deterministic: %s' % ('on' if det['mode'] else 'off'))
