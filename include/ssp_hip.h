@@ -493,7 +493,54 @@ int ssp_upsample_fwd(const float* src, int lds, float* dst, int ldd, int C, int 
 int ssp_upsample_bwd(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride,
                      int accumulate, void* stream);
 
-/* ---- RegionLoss (region_loss.py:9-175, region_loss_multi.py:9-189, utils.py:138-187) ----------------------- */
+/* ---- depthwise 3x3 convolution (appended to ABI 5; csrc/conv_depthwise.hip): nn.Conv2d(C, C, 3, stride, padding 1,
+ * groups = C) at darknet.py:156,160 - a Darknet [convolutional] block with groups = channels = filters - stride 1 or 2, any
+ * position of a net but the first block.  fp32 NHWC maps [pixels][ld], channels fastest; a lane owns one channel quad, every
+ * access is 16 bytes; no matrix cores.  Only columns [0, C) of a row are read or written on either side, so a map may be a
+ * channel slice of a wider buffer (ld > C, the pointer offset by a multiple of 4 floats).  H, W are ALWAYS the sizes of the
+ * block's INPUT map (the data gradient's dx, the filter gradient's x); the output map is Ho x Wo, Ho = (H + 2 - 3)/stride + 1,
+ * Wo likewise; input pixel of output pixel (yo, xo) and tap (r, t) = (stride*yo + r - 1, stride*xo + t - 1), tap = 3 r + t,
+ * zero outside the map - a tap never reads a neighbouring row's or image's pixel.
+ * The filter operand `w` is the parameter's own memory, (C, 1, 3, 3) contiguous: w[c*9 + tap]; the filter gradient `dw` has
+ * the same layout (the parameter's range of the flat gradient buffer).  No repacked operand, no plan code, no state.
+ * Limits of all entry points: C > 0 and C % 4 == 0; leading dimensions % 4 == 0 and >= C; operands (bias / scale / shift /
+ * stats / workspace included, where given) 16-byte aligned; stride 1 or 2; B*H*W < 2^31; workspace_floats >= the query -
+ * anything else is SSP_ERR_ARG with a message and nothing is launched (the queries return 0 on bad sizes).
+ *   forward: out[po][c] = sum_tap in[gather(po, tap)][c] * w[c*9 + tap] (+ bias[c]): the nine products are added with fp32
+ *     fused multiply-adds in ascending tap order from 0, the bias last.  Every input value is loaded once per thread and
+ *     serves all taps of a strip of four output pixels of one row.  The _affine form is the eval-mode block in one launch,
+ *     out = leaky(scale[c] * conv + shift[c], slope), scale / shift nullable (= 1 / 0), slope = 1 for a linear block.
+ *     stats (nullable): per-tile (mean, M2) pairs of the stored output in the COUNTED format of ssp_bn_fwd_finalize -
+ *     ssp_dwconv_stats_tile_m returns 0; the buffer holds [ssp_dwconv_stats_tiles][C][2] pairs followed by
+ *     [ssp_dwconv_stats_tiles] pixel counts (ssp_dwconv_stats_floats floats in all) and the finalize takes tile_m = 0,
+ *     M = B*Ho*Wo.  A tile = max(1, min(64, 1024 / (C/4))) consecutive strips (b, yo, four xo; a row's last strip partial) in
+ *     row-major order.  Per channel: (mean, M2) of a strip's <= 4 values, strips Chan-combined in ascending order within
+ *     max(1, 256 / C) equal parts of the tile, parts combined in ascending order - fp32, a fixed order, no atomics.
+ *   data gradient: dx[pi][c] (=|+=) sum over the (po, tap) pairs that read pi of dy[po][c] * w[c*9 + tap].  Stride 1: the
+ *     forward kernel with the taps flipped (products added in DESCENDING tap order).  Stride 2: a gather by the parity of
+ *     pi = (yi, xi) - an even coordinate is reached by tap 1 only, an odd one by taps 0 and 2, so a pixel sums 1, 2, 2 or 4
+ *     products (ascending tap order), never nine masked ones; one thread owns the four pixels of a 2 x 2 block of dx and
+ *     loads its four dy pixels once.  Every element of dx's C columns is written by exactly one thread, no atomics: the same
+ *     bits every run.  accumulate = 1 adds the earlier content last: dx = dx + s.
+ *   filter gradient: dw[c*9 + tap] (=|+=) sum_po dy[po][c] * in[gather(po, tap)][c].  Two launches: workgroups sum fixed
+ *     ranges of strips (ssp_dwconv_wgrad_workspace_floats = ranges * C * 9 floats; ranges <= 512 and a function of the shape
+ *     alone) - a thread its strips in ascending order with fp32 fused multiply-adds, the threads of a range in ascending
+ *     order - into the workspace; the finishing pass adds the ranges of an element in ascending order in float64, rounds
+ *     once, and stores (accumulate = 1: dw = dw + s).  No atomics in either launch: the kernel is its own ordered form. */
+int ssp_dwconv_fwd(const float* in, const float* w, float* out, const float* bias, float* stats, int B, int H, int W, int C,
+                   int ldin, int ldout, int stride, void* stream);
+int ssp_dwconv_fwd_affine(const float* in, const float* w, float* out, const float* scale, const float* shift, float slope,
+                          int B, int H, int W, int C, int ldin, int ldout, int stride, void* stream);
+int ssp_dwconv_stats_tile_m(int B, int H, int W, int C, int stride);   /* 0 = counted format */
+int ssp_dwconv_stats_tiles(int B, int H, int W, int C, int stride);
+int64_t ssp_dwconv_stats_floats(int B, int H, int W, int C, int stride);
+int ssp_dwconv_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int C, int lddy, int lddx, int stride,
+                     int accumulate, void* stream);
+int64_t ssp_dwconv_wgrad_workspace_floats(int B, int H, int W, int C, int stride);
+int ssp_dwconv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int C, int lddy, int ldx, int stride,
+                     int accumulate, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ---- RegionLoss(region_loss.py:9-175, region_loss_multi.py:9-189, utils.py:138-187) ----------------------- */
 /* out, grad: (nB, nA*(2K+1+nC), nH, nW) NCHW contiguous; target: (nB, 50*(2K+3)) float or double on the device;
  * partials: nB*8 floats; stats[8] = {loss_x, loss_y, loss_conf, loss_cls, total, nGT, nCorrect, nProposals}. */
 int ssp_region_loss(const float* out, const void* target, int target_is_f64, float* grad, float* partials,

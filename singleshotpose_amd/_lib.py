@@ -106,6 +106,14 @@ _SIGS = {
     "ssp_softmax_bwd": [P, I, P, I, P, I, I, L, I, P],
     "ssp_upsample_fwd": [P, I, P, I, I, I, I, I, I, P],
     "ssp_upsample_bwd": [P, I, P, I, I, I, I, I, I, I, P],
+    "ssp_dwconv_fwd": [P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "ssp_dwconv_fwd_affine": [P, P, P, P, P, F, I, I, I, I, I, I, I, P],
+    "ssp_dwconv_stats_tile_m": [I, I, I, I, I],
+    "ssp_dwconv_stats_tiles": [I, I, I, I, I],
+    "ssp_dwconv_stats_floats": [I, I, I, I, I],
+    "ssp_dwconv_dgrad": [P, P, P, I, I, I, I, I, I, I, I, P],
+    "ssp_dwconv_wgrad_workspace_floats": [I, I, I, I, I],
+    "ssp_dwconv_wgrad": [P, P, P, I, I, I, I, I, I, I, I, P, L, P],
     "ssp_region_loss": [P, P, I, P, P, P, I, I, I, I, I, I, F, F, F, F, F, I, I, P, I, P],
     "ssp_region_decode_argmax": [P, P, I, I, I, I, I, I, I, P],
     "ssp_region_decode_all": [P, P, I, I, I, I, I, I, P],
@@ -127,7 +135,8 @@ _SIGS = {
 
 _RET64 = ('ssp_conv_workspace_floats', 'ssp_conv_dgrad_adj_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats', 'ssp_conv_wgrad_wino_workspace_floats_t',
           'ssp_conv_stats_floats', 'ssp_conv_wino_tiles', 'ssp_conv_wgrad_ordered_workspace_floats',
-          'ssp_conv_wgrad_wino_ordered_workspace_floats', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles')
+          'ssp_conv_wgrad_wino_ordered_workspace_floats', 'ssp_first_wgrad_workspace_floats', 'ssp_adds_workspace_doubles', 'ssp_dwconv_stats_floats',
+          'ssp_dwconv_wgrad_workspace_floats')
 
 PROF_KINDS = ("conv_fwd", "conv_dgrad", "conv_wgrad", "bn_act", "layout", "region", "optim", "first_block_fwd",
               "first_block_bwd", "wino_fwd", "wino_dgrad", "wino_wgrad", "onchip_fwd", "onchip_dgrad", "onchip_wgrad")

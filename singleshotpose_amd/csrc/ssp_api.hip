@@ -126,6 +126,17 @@ int ssp_upsample_fwd_launch(const float* src, int lds_, float* dst, int ldd, int
                             hipStream_t stream);
 int ssp_upsample_bwd_launch(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride,
                             int accumulate, hipStream_t stream);
+int ssp_dwconv_fwd_launch(const char* name, const float* in, const float* w, float* out, const float* scale, const float* shift,
+                          float slope, float* stats, int B, int H, int W, int C, int ldin, int ldout, int stride,
+                          hipStream_t stream);
+int ssp_dwconv_stats_tile_m_q(int B, int H, int W, int C, int stride);
+int ssp_dwconv_stats_tiles_q(int B, int H, int W, int C, int stride);
+int64_t ssp_dwconv_stats_floats_q(int B, int H, int W, int C, int stride);
+int ssp_dwconv_dgrad_launch(const float* dy, const float* w, float* dx, int B, int H, int W, int C, int lddy, int lddx,
+                            int stride, int accumulate, hipStream_t stream);
+int64_t ssp_dwconv_wgrad_workspace_floats_q(int B, int H, int W, int C, int stride);
+int ssp_dwconv_wgrad_launch(const float* dy, const float* x, float* dw, int B, int H, int W, int C, int lddy, int ldx, int stride,
+                            int accumulate, float* workspace, int64_t workspace_floats, hipStream_t stream);
 int ssp_region_loss_launch(const float* out, const void* target, int target_is_f64, float* grad, float* partials,
                            float* stats, int nB, int nA, int nC, int nH, int nW, int num_keypoints,
                            float noobject_scale, float object_scale, float coord_scale, float class_scale, float thresh,
@@ -608,6 +619,32 @@ int ssp_upsample_fwd(const float* src, int lds, float* dst, int ldd, int C, int 
 int ssp_upsample_bwd(const float* g, int ldg, float* dsrc, int ldds, int C, int B, int H, int W, int stride, int accumulate,
                      void* stream) {
   return ssp_upsample_bwd_launch(g, ldg, dsrc, ldds, C, B, H, W, stride, accumulate, (hipStream_t)stream);
+}
+
+int ssp_dwconv_fwd(const float* in, const float* w, float* out, const float* bias, float* stats, int B, int H, int W, int C,
+                   int ldin, int ldout, int stride, void* stream) {
+  return ssp_dwconv_fwd_launch("dwconv_fwd", in, w, out, nullptr, bias, 1.f, stats, B, H, W, C, ldin, ldout, stride,
+                               (hipStream_t)stream);
+}
+int ssp_dwconv_fwd_affine(const float* in, const float* w, float* out, const float* scale, const float* shift, float slope,
+                          int B, int H, int W, int C, int ldin, int ldout, int stride, void* stream) {
+  return ssp_dwconv_fwd_launch("dwconv_fwd_affine", in, w, out, scale, shift, slope, nullptr, B, H, W, C, ldin, ldout, stride,
+                               (hipStream_t)stream);
+}
+int ssp_dwconv_stats_tile_m(int B, int H, int W, int C, int stride) { return ssp_dwconv_stats_tile_m_q(B, H, W, C, stride); }
+int ssp_dwconv_stats_tiles(int B, int H, int W, int C, int stride) { return ssp_dwconv_stats_tiles_q(B, H, W, C, stride); }
+int64_t ssp_dwconv_stats_floats(int B, int H, int W, int C, int stride) { return ssp_dwconv_stats_floats_q(B, H, W, C, stride); }
+int ssp_dwconv_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int C, int lddy, int lddx, int stride,
+                     int accumulate, void* stream) {
+  return ssp_dwconv_dgrad_launch(dy, w, dx, B, H, W, C, lddy, lddx, stride, accumulate, (hipStream_t)stream);
+}
+int64_t ssp_dwconv_wgrad_workspace_floats(int B, int H, int W, int C, int stride) {
+  return ssp_dwconv_wgrad_workspace_floats_q(B, H, W, C, stride);
+}
+int ssp_dwconv_wgrad(const float* dy, const float* x, float* dw, int B, int H, int W, int C, int lddy, int ldx, int stride,
+                     int accumulate, float* workspace, int64_t workspace_floats, void* stream) {
+  return ssp_dwconv_wgrad_launch(dy, x, dw, B, H, W, C, lddy, ldx, stride, accumulate, workspace, workspace_floats,
+                                 (hipStream_t)stream);
 }
 
 int ssp_region_loss(const float* out, const void* target, int target_is_f64, float* grad, float* partials,

@@ -118,12 +118,18 @@ class Darknet(nn.Module):
                 bn = int(block['batch_normalize'])
                 filters, k, stride = int(block['filters']), int(block['size']), int(block['stride'])
                 pad = (k - 1) // 2 if int(block['pad']) else 0
+                # Darknet's groups= (default 1): the parameter is (filters, prev_filters / groups, k, k), which is also what
+                # the .weights format holds.  engine.Plan runs groups = prev_filters = filters at 3x3 (depthwise,
+                # csrc/conv_depthwise.hip) and refuses every other grouping by name.
+                groups = int(block.get('groups', 1))
+                if groups < 1 or prev_filters % groups or filters % groups:
+                    raise NotImplementedError("block %d (convolutional): groups=%d does not divide its %d input channels and "
+                                              "%d filters" % (len(models), groups, prev_filters, filters))
                 model = nn.Sequential()
+                model.add_module('conv{0}'.format(conv_id),
+                                 nn.Conv2d(prev_filters, filters, k, stride, pad, groups=groups, bias=not bn))
                 if bn:
-                    model.add_module('conv{0}'.format(conv_id), nn.Conv2d(prev_filters, filters, k, stride, pad, bias=False))
                     model.add_module('bn{0}'.format(conv_id), nn.BatchNorm2d(filters, eps=1e-4))
-                else:
-                    model.add_module('conv{0}'.format(conv_id), nn.Conv2d(prev_filters, filters, k, stride, pad))
                 # Filters are kept channels-last in memory ([Cout][kh][kw][Cin]; shape, values and the .weights format
                 # are unchanged): that is the forward GEMM operand and the layout the filter gradient is accumulated in,
                 # so the kernels use parameter and gradient in place instead of repacking 202 MB three times a step.
@@ -131,7 +137,8 @@ class Darknet(nn.Module):
                 # (Layers whose input channels are not a multiple of 4 - the 3-channel first layer - are padded on the
                 # way to the kernels, so they keep the plain layout and the small repack.)
                 conv = model[0]
-                if prev_filters % 4 == 0:
+                # (A grouped filter stays plain contiguous: the depthwise kernels read (C, 1, 3, 3) as w[c*9 + tap].)
+                if prev_filters % 4 == 0 and groups == 1:
                     conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
                 if block['activation'] == 'leaky':
                     model.add_module('leaky{0}'.format(conv_id), nn.LeakyReLU(0.1, inplace=True))

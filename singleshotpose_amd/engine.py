@@ -11,6 +11,8 @@ A max-pool block is fused into the preceding conv block when nothing else consum
 route = alias or ssp_copy_channels into a concat buffer; reorg = ssp_reorg.
 upsample = ssp_upsample_fwd / ssp_upsample_bwd (csrc/upsample.hip): nearest-neighbour replication, written straight into the
 concatenation buffer of the two-layer route behind it when that route is its only consumer (Plan.upsample).
+A [convolutional] block with groups = channels = filters (depthwise 3x3, stride 1 or 2) runs ssp_dwconv_fwd / _dgrad / _wgrad
+(csrc/conv_depthwise.hip) on the (C, 1, 3, 3) parameter itself, inside the same BatchNorm / activation / pool chain (Plan.depthwise).
 The other Darknet blocks (darknet.py:8-47, :107-118, :168-229) run on csrc/generic_blocks.hip: stride-1 max-pool, shortcut,
 global average pool, softmax over channels; a connected block is planned as a 1x1 convolution of its (B, Cin) input on a 1x1
 map (M = B rows: the conv kernels, bias and activation path of a non-BN conv block).
@@ -212,6 +214,8 @@ class _ConvSpec(object):
     bn_train = False               # the last forward normalised this block with batch statistics (its BatchNorm's own mode)
     has_raw = False                # ... and left the raw conv output behind (what a backward through the block needs)
     fsched = None                  # the block's OpSchedule of the last forward that kept gradient bookkeeping
+    depthwise = False              # groups = channels = filters, 3x3: csrc/conv_depthwise.hip on the parameter's own memory -
+                                   # no packed / transformed operand, no plan code, no tuner entry (as a stride-2 block)
 
     @property
     def oind(self):
@@ -308,8 +312,31 @@ class Plan(object):
             w, h, c = self.shapes[ind]
             zeros_or_empty = torch.empty if _pad4(c) == c else torch.zeros     # padding channels stay zero
             if t in ('convolutional', 'connected'):
+                groups = 1
                 if t == 'convolutional':
                     k, s = int(block['size']), int(block['stride'])
+                    groups = int(block.get('groups', 1))
+                    if groups != 1:
+                        # depthwise 3x3 (csrc/conv_depthwise.hip) is the one grouped convolution that is built
+                        cin_ = in_c if prev is self.input_act else prev.C
+                        why = None
+                        if groups != cin_:
+                            why = "groups=%d on a %d-channel map (only groups=1 and the depthwise groups=%d are built)" % (
+                                groups, cin_, cin_)
+                        elif c != cin_:
+                            why = "a depthwise convolution with filters=%d on %d channels (a channel multiplier is not built)" % (
+                                c, cin_)
+                        elif k != 3 or not int(block['pad']):
+                            why = "a depthwise convolution with size=%d pad=%s (only size=3 pad=1 is built)" % (k, block['pad'])
+                        elif prev is self.input_act:
+                            why = ("a depthwise convolution on the network input (the first block's kernels are dense; "
+                                   "csrc/conv_depthwise.hip serves every later position)")
+                        elif cin_ % 4:
+                            why = "a depthwise convolution on a %d-channel map (ssp_dwconv_fwd needs a multiple of 4)" % cin_
+                        elif s not in (1, 2):
+                            why = "a depthwise convolution with stride=%d (1 or 2)" % s
+                        if why is not None:
+                            raise NotImplementedError("block %d (convolutional): %s" % (ind, why))
                     if s not in (1, 2) or k not in (1, 3) or (k == 3 and not int(block['pad'])):
                         raise NotImplementedError("conv size=%d stride=%d pad=%s is outside the yolo-pose hot path" % (k, s, block['pad']))
                     if s == 2 and prev is self.input_act:
@@ -342,9 +369,11 @@ class Plan(object):
                 cs.cin = in_c if cs.first else prev.C
                 cs.cinp = _pad4(cs.cin)
                 cs.cout = c
-                if conv.weight.shape[1] != cs.cin:
-                    raise NotImplementedError("block %d (%s): its parameter takes %d input channels but the map it is given "
-                                              "has %d" % (ind, t, conv.weight.shape[1], cs.cin))
+                cs.depthwise = groups != 1
+                if conv.weight.shape[1] * groups != cs.cin or getattr(conv, 'groups', 1) != groups:
+                    raise NotImplementedError("block %d (%s): its parameter takes %d input channels in %d group(s) but the map "
+                                              "it is given has %d (cfg groups=%d)" % (ind, t, conv.weight.shape[1] * getattr(
+                                                  conv, 'groups', 1), getattr(conv, 'groups', 1), cs.cin, groups))
                 if prev.ld < cs.cinp:
                     raise NotImplementedError("block %d (%s): its %d-channel input map has a row stride of %d floats, narrower "
                                               "than the padded channel count %d" % (ind, t, cs.cin, prev.ld, cs.cinp))
@@ -380,7 +409,7 @@ class Plan(object):
                     cs.vec[2].fill_(1.0)
                 cs.woff, cs.doff = wsz, dsz
                 wsz += c * k * k * cs.cinp
-                dsz += cs.cinp * k * k * cs.coutp if not cs.first else 0
+                dsz += cs.cinp * k * k * cs.coutp if not (cs.first or cs.depthwise) else 0
                 self.convs[ind] = cs
                 if cs.pool:
                     self.fused_pool.add(ind + 1)
@@ -484,6 +513,9 @@ class Plan(object):
             self.ops.append(op)
             self._place(op.oind, op.out)
             prev = op.out
+        # the depthwise 3x3 blocks (csrc/conv_depthwise.hip), by layer: the record tools/show_plans.py prints
+        self.depthwise = sorted(i for i, cs in self.convs.items() if cs.depthwise)
+        self._dw_ws = None         # partial sums of the depthwise filter gradients: one buffer, they share a stream
         o = self.acts[self.last]
         if o.ld > o.C:
             # (the gradient of the output arrives NCHW and is laid out with ld = C by Plan.backward)
@@ -571,6 +603,8 @@ class Plan(object):
         B = self.B
         if cs.first_fused:
             return ('first-block', 0, _lib.query('ssp_first_groups', B, cs.H, cs.W))      # per-workgroup partials, float64 finalize
+        if cs.depthwise:      # its only form: per-range partials, float64 finish (the ranges follow from the shape)
+            return ('depthwise', 0, _lib.query('ssp_dwconv_wgrad_workspace_floats', B, cs.Hi, cs.Wi, cs.cin, cs.stride) // (9 * cs.cin))
         if cs.wgrad_wino:
             return ('winograd-ordered', cs.wgrad_wino,
                     _lib.query('ssp_conv_wgrad_wino_ordered_split', B, cs.H, cs.W, cs.cinp, cs.cout, cs.wgrad_wino, 0))
@@ -590,6 +624,8 @@ class Plan(object):
             cs.wgrad_det = self._wgrad_split(cs)
             if cs.first:
                 dg = 'first-block' if cs.first_fused else 'direct'
+            elif cs.depthwise:
+                dg = 'depthwise' if cs.stride == 1 else 'depthwise-stride2'      # one thread per element, no atomics
             elif cs.stride == 2:
                 dg = 'stride2-ordered'
             else:
@@ -611,9 +647,18 @@ class Plan(object):
         if self._wgrad_ws is None:
             need = max([1] + [_lib.query('ssp_conv_wgrad_ordered_workspace_floats', self.B, cs.Hi, cs.Wi, cs.cinp, cs.cout,
                                          cs.ldraw, cs.inp.ld, cs.k, cs.stride, 0)
-                              for cs in self.convs.values() if not cs.first_fused])
+                              for cs in self.convs.values() if not (cs.first_fused or cs.depthwise)])
             self._wgrad_ws = torch.empty(need, dtype=torch.float32, device=self.device)
         return self._wgrad_ws
+
+    def _dwconv_ws(self):
+        """The per-range partial sums of the depthwise filter gradients (ssp_dwconv_wgrad), allocated on the first backward
+        and sized for the largest layer: the launches of one backward are queued on one stream."""
+        if self._dw_ws is None:
+            need = max([1] + [_lib.query('ssp_dwconv_wgrad_workspace_floats', self.B, cs.Hi, cs.Wi, cs.cin, cs.stride)
+                              for cs in self.convs.values() if cs.depthwise])
+            self._dw_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._dw_ws
 
     def _place(self, ind, act):
         """acts[ind] = act; the first layer to hold a map is its producer (see _Act)."""
@@ -627,6 +672,14 @@ class Plan(object):
         counted format of a Winograd launch), their count, the launch's workspace need; the statistics buffer is sized
         for the largest format any timed family of the layer uses, so a plan change never re-allocates it."""
         B = self.B
+        if cs.depthwise:         # no plan codes, no workspace: the counted format (tile_m = 0)
+            cs.tile_m = _lib.query('ssp_dwconv_stats_tile_m', B, cs.Hi, cs.Wi, cs.cin, cs.stride)
+            cs.ntile = _lib.query('ssp_dwconv_stats_tiles', B, cs.Hi, cs.Wi, cs.cin, cs.stride)
+            cs.ws_fwd = 0
+            if cs.bn and cs.stats is None:
+                cs.stats = torch.empty(_lib.query('ssp_dwconv_stats_floats', B, cs.Hi, cs.Wi, cs.cin, cs.stride),
+                                       dtype=torch.float32, device=self.device)
+            return
         if cs.stride == 2:       # no plan codes, no workspace: one tile format (ssp_conv_s2_stats_tile_m)
             cs.tile_m = _lib.query('ssp_conv_s2_stats_tile_m', B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.k)
             cs.ntile = _lib.query('ssp_conv_s2_stats_tiles', B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.k)
@@ -677,7 +730,7 @@ class Plan(object):
         stale, self._stale = self._stale, set()
         if dgrad or 'dgrad' in stale:
             for cs in self.convs.values():
-                cs.ws_dgrad = 0 if (cs.first or cs.stride == 2) else _lib.query(
+                cs.ws_dgrad = 0 if (cs.first or cs.stride == 2 or cs.depthwise) else _lib.query(
                     'ssp_conv_workspace_floats', self.B, cs.H, cs.W, cs.coutp, cs.cin, cs.k, cs.plan_dgrad)
             self._plan_bn_fusion()
         self._fit_workspace()
@@ -873,7 +926,7 @@ class Plan(object):
     def _x3_code(self, cs, which):
         """The rule above as one function of a layer's forward / data-gradient launch: the code to run instead of the
         launch's own fp32 code, or 0 = that one stays."""
-        if self.conv_math['mode'] == 'fp32' or cs.first or cs.stride != 1:
+        if self.conv_math['mode'] == 'fp32' or cs.first or cs.stride != 1 or cs.depthwise:
             return 0
         own = self._own_code(cs, which)
         if wino_tile(own):
@@ -1041,7 +1094,7 @@ class Plan(object):
     def nbytes_now(self):
         """Bytes of device memory the plan holds right now: forward buffers, and whatever the first backward and the tuner
         added since (gradient buffers, data-gradient operands, Winograd filters and per-layer workspaces)."""
-        ts = self._forward_tensors() + [self._dpack, self._wgrad_ws] + [g.t for g in self.grads.values()]
+        ts = self._forward_tensors() + [self._dpack, self._wgrad_ws, self._dw_ws] + [g.t for g in self.grads.values()]
         for cs in self.convs.values():
             ts += [cs.wbuf, cs.gbuf, cs.wino_ws, cs.first_wpart, cs.bnp[0] if cs.bnp is not None else None]
             ts += list((cs.wino_u or {}).values()) + list((cs.wino_ud or {}).values())
@@ -1109,7 +1162,7 @@ class Plan(object):
         elif self._tune:
             kn = knobs()
             for cs in self.convs.values():
-                if cs.stride != 1:      # no plan codes (and its key would be a stride-1 layer's of the same shape)
+                if cs.stride != 1 or cs.depthwise:      # no plan codes (and its key would be a stride-1 layer's of the same shape)
                     continue
                 key = self._dgrad_key(cs)
                 # (the code that was verified, not just the key: a cached Winograd code that SSP_WINOGRAD=0 kept out of
@@ -1161,7 +1214,9 @@ class Plan(object):
         if not on:
             return
         for cs in self.convs.values():
-            if cs.first or cs.stride != 1:      # (the strided data gradient has no fused sums: its producer keeps two passes)
+            # (the strided and the depthwise data gradients have no fused sums: their producers keep two passes; either may
+            # be the SOURCE of a pair)
+            if cs.first or cs.stride != 1 or cs.depthwise:
                 continue
             src = cs.inp.producer
             scs = self.convs.get(src)
@@ -1181,6 +1236,8 @@ class Plan(object):
             scs.bnp = (torch.zeros(rows * scs.cout * 2, dtype=torch.float32, device=self.device), rows, ntile > rows)
 
     def _repack_dgrad(self, cs, stream):
+        if cs.depthwise:      # ssp_dwconv_dgrad reads the parameter itself
+            return
         src = cs.conv.weight.detach()
         if not cs.packed:
             with torch.cuda.stream(stream):
@@ -1261,6 +1318,13 @@ class Plan(object):
         stale = []
         for cs in self.convs.values():
             wt = cs.conv.weight
+            if cs.depthwise:
+                # the (C, 1, 3, 3) parameter IS the operand, w[c*9 + tap], and its gradient is written in that layout in place
+                if not wt.is_contiguous():
+                    raise RuntimeError("block %d (convolutional): the depthwise filter is not contiguous (ssp_dwconv_fwd reads "
+                                       "the (C, 1, 3, 3) parameter in place)" % cs.ind)
+                cs.packed = True
+                continue
             cs.packed = _is_packed(wt, cs.cinp)
             if cs.packed:
                 continue
@@ -1433,6 +1497,10 @@ class Plan(object):
             # inference, un-pooled block: BatchNorm affine + leaky folded into the conv epilogue - one launch,
             # no raw-output round trip (backward needs the raw output, so training / autograd keep two steps).  Also
             # a block with its BatchNorm in eval() that no backward will visit (a frozen trunk under model.train()).
+            if cs.depthwise:
+                call('ssp_dwconv_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
+                     v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.Hi, cs.Wi, cs.cin, cs.inp.ld, cs.out.ld, cs.stride, st)
+                return
             if cs.stride == 2:
                 call('ssp_conv_s2_fwd_affine', cs.inp.ptr, wptr, cs.out.ptr, v[2].data_ptr() if cs.bn else None,
                      v[3].data_ptr() if cs.bn else bias, cs.slope, B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.inp.ld,
@@ -1465,7 +1533,10 @@ class Plan(object):
             call('ssp_wino_input_transform_t', cs.inp.ptr, cs.inp.ld, wws.data_ptr(), B, cs.H, cs.W, cs.cinp,
                  cs.wgrad_wino, self.side_stream.cuda_stream)
             cs.v_live = True
-        if cs.stride == 2:
+        if cs.depthwise:
+            call('ssp_dwconv_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias, cs.stats.data_ptr() if use_stats else None,
+                 B, cs.Hi, cs.Wi, cs.cin, cs.inp.ld, cs.ldraw, cs.stride, st)
+        elif cs.stride == 2:
             call('ssp_conv_s2_fwd', cs.inp.ptr, wptr, cs.raw.data_ptr(), bias, cs.stats.data_ptr() if use_stats else None,
                  B, cs.Hi, cs.Wi, cs.cinp, cs.cout, cs.inp.ld, cs.ldraw, cs.k, 0, st)
         else:
@@ -1621,6 +1692,13 @@ class Plan(object):
         call = _lib.call
         B = self.B
         gin = self._grad_buf(src, cs.inp)
+        if cs.depthwise:
+            # csrc/conv_depthwise.hip: H x W of the INPUT map, the parameter itself as the operand, one thread per element
+            # at both strides (the same bits every run: deterministic mode needs no other form)
+            call('ssp_dwconv_dgrad', dy_ptr, cs.conv.weight.data_ptr(), gin.ptr, B, cs.Hi, cs.Wi, cs.cin, dy_ld, gin.ld,
+                 cs.stride, 1 if src in written else 0, st)
+            written.add(src)
+            return
         if cs.stride == 2:
             # parity-decomposed data gradient (csrc/conv_strided.hip): H x W of the INPUT map, no plan, no workspace, no
             # fused BatchNorm-backward sums (_plan_bn_fusion never makes a strided block the consumer)
@@ -1947,7 +2025,13 @@ class Plan(object):
                          cs.k, cs.stride, cs.wgrad_det[2], 0, ows.data_ptr(), ows.numel(), st2)
                 else:
                     call(wg_name, dy_ptr, cs.inp.ptr, dst, B, cs.Hi, cs.Wi, cs.cinp, cs.cout, dy_ld, cs.inp.ld, cs.k, st2)
-            if cs.packed and cs.wgrad_wino:
+            if cs.depthwise:
+                # per-range partials, then a float64 finish that WRITES the (C, 1, 3, 3) gradient in place (no atomics: the
+                # launch is its own ordered form)
+                dws = self._dwconv_ws()
+                call('ssp_dwconv_wgrad', dy_ptr, cs.inp.ptr, gw.data_ptr(), B, cs.Hi, cs.Wi, cs.cin, dy_ld, cs.inp.ld, cs.stride,
+                     0, dws.data_ptr(), dws.numel(), st2)
+            elif cs.packed and cs.wgrad_wino:
                 wws = self._wino_ws(cs)
                 # (dy = NULL: dM is in its slot of wws already, see above)
                 wargs = (None if dm_ptr is not None else dy_ptr, None if cs.v_live else cs.inp.ptr, gw.data_ptr(), B, cs.H, cs.W,

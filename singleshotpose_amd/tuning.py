@@ -187,7 +187,7 @@ def wino_forms(kn, cs, B, min_channels=0, min_tiles=0, halo_rows=0):
     the on-chip F(2x2) kernels at 32-channel granularity while every byte offset of the maps stays below 2^31.  Forward and data
     gradient take the defaults; the filter gradient asks min_channels=64 and min_tiles=16 (B * ceil(H/t) * ceil(W/t)) of its
     through-memory forms, and its on-chip form (csrc/conv_wino_wgrad_fused.hip) reads halo_rows = W + 1 pixels past the map."""
-    if not (kn.wino_on and cs.k == 3 and cs.stride == 1 and not cs.first and cs.cinp == cs.cin and cs.coutp == cs.cout and
+    if not (kn.wino_on and cs.k == 3 and cs.stride == 1 and not cs.first and not cs.depthwise and cs.cinp == cs.cin and cs.coutp == cs.cout and
             cs.cin % 16 == 0 and cs.cout % 16 == 0):
         return (), False
     cmin = min(cs.cin, cs.cout)
@@ -525,8 +525,8 @@ def _tune_x3_wino(plan, kn, sc, cs, probe, key, fp32_code):
 
 
 def tunable(plan):
-    """The layers whose forward / data-gradient launches take plan codes: stride 1, input channels a multiple of 16."""
-    return [cs for cs in plan.convs.values() if cs.cinp % 16 == 0 and cs.stride == 1]
+    """The layers whose forward / data-gradient launches take plan codes: dense, stride 1, input channels a multiple of 16."""
+    return [cs for cs in plan.convs.values() if cs.cinp % 16 == 0 and cs.stride == 1 and not cs.depthwise]
 
 
 def tune_convs(plan, which):

@@ -32,6 +32,10 @@ for ind, cs in sorted(plan.convs.items()):
     print('layer %2d  %4dx%-4d %4d->%-4d k%d  fwd %7d %-14s  dgrad %7d %-14s  wgrad %s' % (
         ind, cs.H, cs.W, cs.cin, cs.cout, cs.k, cs.plan_fwd, family(cs.plan_fwd), cs.plan_dgrad, family(cs.plan_dgrad),
         ('winograd F(%dx%d)' % (cs.wgrad_wino, cs.wgrad_wino)) if getattr(cs, 'wgrad_wino', 0) else 'direct'))
+for ind in plan.depthwise:      # groups = channels: csrc/conv_depthwise.hip at all three launches (the codes above do not apply)
+    cs = plan.convs[ind]
+    print('layer %2d  depthwise 3x3 / %d on %dx%d x%d -> %dx%d, statistics tiles %d' % (
+        ind, cs.stride, cs.Hi, cs.Wi, cs.cin, cs.H, cs.W, cs.ntile))
 for ind, form in sorted(plan.upsample.items()):      # 'route': written into the concatenation buffer of the route behind it
     a = plan.acts[ind]
     print('layer %2d  upsample x%s -> %dx%d x%d, row stride %d: %s' % (
