@@ -27,15 +27,17 @@ def test_the_topology_selection_has_routes_shortcuts_and_a_dead_branch():
 
 
 # ---------------------------------------------------------------------------------------------------- the rules, restated
-def _expected(blocks, B, H, W, own, want_input, bn_train):
+def _expected(blocks, B, H, W, own, want_input, bn_train, fuse=None):
     """Per layer of the cfg: visited, data gradient per source, and for conv blocks (wgrad, bias, dgamma, dbeta, bn_reduce,
-    fold_bn).  own: {conv layer: (weight, bias, gamma, beta) trainable}; bn_train: {conv layer: BatchNorm in training mode}."""
+    fold_bn).  own: {conv layer: (weight, bias, gamma, beta) trainable}; bn_train: {conv layer: BatchNorm in training mode};
+    fuse: the {consumer: source} BatchNorm pairs, for cfgs with blocks T.expected_bn_fuse does not know (groups=)."""
     info = T.layer_info(blocks, H, W)
     live = T.live_layers(info)
     rel = {-1: bool(want_input)}
     for i, l in enumerate(info):
         rel[i] = any(own.get(i, ())) or any(rel[s] for s in l.srcs)
-    fuse = T.expected_bn_fuse(blocks, B, H, W)
+    if fuse is None:
+        fuse = T.expected_bn_fuse(blocks, B, H, W)
     out = {}
     for i, l in enumerate(info):
         visited = i in live and rel[i]
