@@ -383,6 +383,61 @@ int ssp_sgd_step_table(float* param, const float* grad, float* momentum_buf, int
                        int64_t momentum_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
                        const float* hyper, int ntuple, void* stream);
 
+/* One torch.optim.Adam / AdamW step over a contiguous fp32 range of n values, in place.  param, grad, exp_avg (m),
+ * exp_avg_sq (v) and max_exp_avg_sq (vmax; non-NULL iff amsgrad) are 16-byte aligned.  Per element, in the order of
+ * torch/optim/adam.py's single-tensor path:
+ *   decoupled (AdamW):  p = p * (1 - lr*weight_decay)        else (Adam):  g = fma(weight_decay, p, g)
+ *                       (both only when weight_decay != 0)
+ *   m = fma(1 - beta1, g - m, m)
+ *   v = fma((1 - beta2)*g, g, beta2*v)
+ *   amsgrad:  vmax = max(vmax, v) (a NaN propagates);  d = vmax          else:  d = v
+ *   denom = sqrt(d) / bc2_sqrt + eps
+ *   p = p + (-step_size * m) / denom          (= p - step_size * (m / denom); product, quotient and sum each rounded,
+ *                                              as torch's addcdiv_ does)
+ * Every operation written here is rounded once to fp32 (nothing else is contracted); sqrt and `/` are the IEEE correctly
+ * rounded ones.  The hyper-parameters travel by value as doubles; 1 - lr*weight_decay, 1 - beta1, 1 - beta2 and
+ * -step_size are formed in double and rounded to fp32 once, as are the others.  The caller owns the step count t and
+ * passes step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t); the kernel never sees t.
+ * SSP_ERR_ARG before any launch: a NULL param / grad / m / v or n < 1, a misaligned pointer, amsgrad without vmax,
+ * beta1 or beta2 outside [0, 1), eps <= 0 (also when it rounds to 0 in fp32), lr or weight_decay negative or not
+ * finite, a step_size that is not finite, a bc2_sqrt that is not finite or <= 0. */
+int ssp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, double step_size,
+                  double bc2_sqrt, int decoupled, int amsgrad, void* stream);
+#define SSP_ADAM_MAX_TUPLES 16
+/* The same update over a TABLE of segments in one launch, as ssp_sgd_step_table: segment s is table[s] = {param offset,
+ * grad offset, state offset, length, tuple index} (five int64, in floats; offsets multiples of 4, lengths arbitrary); the
+ * state offset serves exp_avg, exp_avg_sq and max_exp_avg_sq, which share one layout of state_floats floats.  Tuple t is
+ * hyper[t] = {lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, decoupled (0 / 1), amsgrad (0 / 1)} (nine
+ * doubles, at most SSP_ADAM_MAX_TUPLES = 16: they travel by value with the launch, so the per-batch lr rewrite and the
+ * per-step bias corrections upload nothing).  Every element is updated exactly as by ssp_adam_step on its segment
+ * (bit-identical).  Before anything is launched every tuple is checked as above and every row of table_host against the
+ * buffer lengths: a negative or misaligned offset, a segment that ends outside a buffer, a length < 1 or a tuple index
+ * outside [0, ntuple) is SSP_ERR_ARG and nothing runs.  Work is dealt in 4096-float chunks round-robin over at most 2048
+ * workgroups.  Segments must not overlap in param / state (not checked). */
+int ssp_adam_step_table(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                        int64_t param_floats, int64_t grad_floats, int64_t state_floats, const int64_t* table_dev,
+                        const int64_t* table_host, int nseg, const double* hyper, int ntuple, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) as two launches on one stream, with no
+ * host synchronisation and no atomics: the same inputs give the same bits on every run.  Both walk the GRADIENT segments
+ * of a table as above (fields 1 and 3 of a row: grad offset, length; the other fields are not read, and the floats
+ * between segments are never read or written); table_dev = table_host = NULL with nseg = 1 means the one range
+ * [0, grad_floats).
+ * ssp_grad_sumsq_table: every lane adds the squares of its elements in double (an fp32 square is exact in double), the
+ *   256 lane sums of a workgroup are added in LDS by a fixed halving tree, and workgroup b writes partial[b].
+ *   *npartial = the workgroups launched = min(chunks, 2048, partial_capacity).
+ * ssp_grad_scale_table: every workgroup adds partial[0 .. npartial) in one fixed order (lane t adds t, t + 256, ...
+ *   ascending, then the same tree; npartial <= 65536, so several sumsq launches may fill one array), then
+ *   norm = sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) in double (a NaN propagates), coef rounded once to fp32,
+ *   and multiplies its chunks of grad by coef in place (one rounding per element; nothing is written when the rounded
+ *   coef is exactly 1).  Workgroup 0 writes result[0] = (float)norm, result[1] = coef.
+ * SSP_ERR_ARG before any launch: NULL / misaligned buffers, a bad row (as above), no room for partials, npartial outside
+ * [1, 65536], max_norm negative or NaN. */
+int ssp_grad_sumsq_table(const float* grad, int64_t grad_floats, const int64_t* table_dev, const int64_t* table_host,
+                         int nseg, double* partial, int partial_capacity, int* npartial, void* stream);
+int ssp_grad_scale_table(float* grad, int64_t grad_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
+                         const double* partial, int npartial, double max_norm, float* result, void* stream);
+
 /* ---- layout / index kernels -------------------------------------------------------------------------------- */
 int ssp_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* stream);
 int ssp_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, int ld, void* stream);

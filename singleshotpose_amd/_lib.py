@@ -22,6 +22,7 @@ P = c_void_p
 I = c_int
 F = c_float
 L = c_int64
+D = c_double
 
 # name -> argtypes (all return int unless noted)
 _SIGS = {
@@ -82,6 +83,10 @@ _SIGS = {
     "ssp_adds_errors": [P, P, P, I, I, P, P, I, P, P, L, P],
     "ssp_sgd_step": [P, P, P, L, F, F, F, F, I, I, P],
     "ssp_sgd_step_table": [P, P, P, L, L, L, P, P, I, P, I, P],
+    "ssp_adam_step": [P, P, P, P, P, L, D, D, D, D, D, D, D, I, I, P],
+    "ssp_adam_step_table": [P, P, P, P, P, L, L, L, P, P, I, P, I, P],
+    "ssp_grad_sumsq_table": [P, L, P, P, I, P, I, P, P],
+    "ssp_grad_scale_table": [P, L, P, P, I, P, I, D, P, P],
     "ssp_nchw_to_nhwc": [P, P, I, I, I, I, I, I, P],
     "ssp_nhwc_to_nchw": [P, P, I, I, I, I, I, P],
     "ssp_u8hwc_to_nhwc": [P, P, I, I, I, I, I, I, P],

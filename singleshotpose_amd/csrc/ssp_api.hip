@@ -80,6 +80,16 @@ int ssp_sgd_step_launch(float* p, const float* g, float* m, int64_t n, float lr,
 int ssp_sgd_step_table_launch(float* p, const float* g, float* m, int64_t p_floats, int64_t g_floats, int64_t m_floats,
                               const int64_t* table_dev, const int64_t* table_host, int nseg, const float* hyper, int ntuple,
                               hipStream_t stream);
+int ssp_adam_step_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double lr, double beta1,
+                         double beta2, double eps, double weight_decay, double step_size, double bc2_sqrt, int decoupled,
+                         int amsgrad, hipStream_t stream);
+int ssp_adam_step_table_launch(float* p, const float* g, float* m, float* v, float* vmax, int64_t p_floats,
+                               int64_t g_floats, int64_t s_floats, const int64_t* table_dev, const int64_t* table_host,
+                               int nseg, const double* hyper, int ntuple, hipStream_t stream);
+int ssp_grad_sumsq_table_launch(const float* g, int64_t g_floats, const int64_t* table_dev, const int64_t* table_host,
+                                int nseg, double* partial, int partial_capacity, int* npartial, hipStream_t stream);
+int ssp_grad_scale_table_launch(float* g, int64_t g_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
+                                const double* partial, int npartial, double max_norm, float* result, hipStream_t stream);
 int ssp_nchw_to_nhwc_launch(const float* src, float* dst, int B, int C, int H, int W, int Cp, int ld, hipStream_t stream);
 int ssp_nhwc_to_nchw_launch(const float* src, float* dst, int B, int C, int H, int W, int ld, hipStream_t stream);
 int ssp_pose_errors_launch(const double* verts, int N, const double* Rt_gt, const double* Rt_pr, const double* K,
@@ -539,6 +549,28 @@ int ssp_sgd_step_table(float* param, const float* grad, float* momentum_buf, int
                        const float* hyper, int ntuple, void* stream) {
   return ssp_sgd_step_table_launch(param, grad, momentum_buf, param_floats, grad_floats, momentum_floats, table_dev,
                                    table_host, nseg, hyper, ntuple, (hipStream_t)stream);
+}
+int ssp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, double step_size,
+                  double bc2_sqrt, int decoupled, int amsgrad, void* stream) {
+  return ssp_adam_step_launch(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                              step_size, bc2_sqrt, decoupled, amsgrad, (hipStream_t)stream);
+}
+int ssp_adam_step_table(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                        int64_t param_floats, int64_t grad_floats, int64_t state_floats, const int64_t* table_dev,
+                        const int64_t* table_host, int nseg, const double* hyper, int ntuple, void* stream) {
+  return ssp_adam_step_table_launch(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, param_floats, grad_floats,
+                                    state_floats, table_dev, table_host, nseg, hyper, ntuple, (hipStream_t)stream);
+}
+int ssp_grad_sumsq_table(const float* grad, int64_t grad_floats, const int64_t* table_dev, const int64_t* table_host,
+                         int nseg, double* partial, int partial_capacity, int* npartial, void* stream) {
+  return ssp_grad_sumsq_table_launch(grad, grad_floats, table_dev, table_host, nseg, partial, partial_capacity, npartial,
+                                     (hipStream_t)stream);
+}
+int ssp_grad_scale_table(float* grad, int64_t grad_floats, const int64_t* table_dev, const int64_t* table_host, int nseg,
+                         const double* partial, int npartial, double max_norm, float* result, void* stream) {
+  return ssp_grad_scale_table_launch(grad, grad_floats, table_dev, table_host, nseg, partial, npartial, max_norm, result,
+                                     (hipStream_t)stream);
 }
 
 int ssp_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, int Cpad, int ld, void* stream) {

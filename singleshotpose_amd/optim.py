@@ -21,6 +21,11 @@ runs the whole step as ONE ssp_sgd_step launch:
   with the launch, so the per-batch `lr` rewrite uploads nothing; the table is rebuilt only when the layout or the group
   membership changes.  Parameters the optimizer does not hold are never read or written.
 
+`Adam` / `AdamW` (further down) keep torch.optim.Adam's constructor, state keys and update rule on the same flat layout -
+one ssp_adam_step launch, or one ssp_adam_step_table launch for groups, subsets and differing step counts - and
+`clip_grad_norm_` clips the global 2-norm of the flat gradient views in two launches without a host synchronisation
+(DESIGN.md section 1b).
+
 No CPU path: parameters must be on the GPU.
 """
 import ctypes
@@ -304,3 +309,321 @@ class SGD(torch.optim.Optimizer):
         self._first = False
         weights_changed()
         return loss
+
+
+# ---- Adam / AdamW ------------------------------------------------------------------------------------------------------
+# torch.optim.Adam's update (single-tensor order, include/ssp_hip.h: ssp_adam_step) on the same flat layout: a step is ONE
+# ssp_adam_step launch when uniform hyper-parameters and equal step counts cover the backward's whole gradient layout,
+# ONE ssp_adam_step_table launch for groups, a held subset or differing step counts, per-parameter launches of the same
+# kernel otherwise.  The state keeps torch's keys (`step`: a 0-dim float32 CPU tensor, `exp_avg`, `exp_avg_sq`,
+# `max_exp_avg_sq`), so state_dict() loads into torch.optim.Adam / AdamW and theirs into these classes.
+def _bias_corrections(lr, beta1, beta2, step):
+    """(step_size, bc2_sqrt) in Python doubles, exactly as torch/optim/adam.py's single-tensor path forms them."""
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    return lr / bias_correction1, bias_correction2 ** 0.5
+
+
+def build_adam_segment_table(entries, max_tuples=MAX_TUPLES):
+    """The segment table of one ssp_adam_step_table launch - a pure function of what the optimizer holds.
+
+    entries: one (numel, gradient offset, key) per parameter that has a gradient, in optimizer order; gradient offset as
+    in build_segment_table; key = (lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, step) with step the
+    parameter's step count AFTER this step (parameters whose counts differ need different bias corrections).
+
+    Returns None when the per-parameter launches must run instead (a gradient that is no aligned flat view, more than
+    `max_tuples` distinct keys).  Else (rows, keys, flat_numel): rows [[parameter offset, gradient offset, state offset,
+    numel, tuple index]] - parameter and state offsets pack the held parameters in order, each rounded up to 4 floats;
+    keys in order of first use; flat_numel = floats of the parameter (and of each state) buffer."""
+    if not entries:
+        return None
+    index = {}
+    rows = []
+    off = 0
+    for numel, goff, key in entries:
+        if goff is None or goff % 4 or goff < 0 or numel < 1:
+            return None
+        key = tuple(float(k) for k in key[:5]) + (bool(key[5]), bool(key[6]), float(key[7]))
+        t = index.setdefault(key, len(index))
+        if len(index) > max_tuples:
+            return None
+        rows.append([off, int(goff), off, int(numel), t])
+        off += (int(numel) + 3) // 4 * 4
+    return rows, list(index), off
+
+
+def _hyper9(key):
+    lr, beta1, beta2, eps, wd, decoupled, amsgrad, step = key
+    step_size, bc2_sqrt = _bias_corrections(lr, beta1, beta2, step)
+    return (lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, 1.0 if decoupled else 0.0, 1.0 if amsgrad else 0.0)
+
+
+class Adam(torch.optim.Optimizer):
+    _decoupled = False
+    _name = 'Adam'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("%s: a tensor lr is not supported (lr travels by value with the launch)" % self._name)
+        for name, value in (('maximize', maximize), ('capturable', capturable), ('differentiable', differentiable),
+                            ('foreach', foreach), ('fused', fused)):
+            if value:
+                raise ValueError("%s: %s=%r is not supported: the step is this project's own fused HIP launch"
+                                 % (self._name, name, value))
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: %s" % lr)
+        if not 0.0 < eps:
+            raise ValueError("Invalid epsilon value: %s (the HIP kernel needs eps > 0)" % eps)
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: %s" % betas[0])
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: %s" % betas[1])
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: %s" % weight_decay)
+        # torch's own group keys, so that a state_dict moves between these classes and torch's in both directions
+        defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
+                        amsgrad=bool(amsgrad), maximize=False, foreach=None, capturable=False, differentiable=False,
+                        fused=None, decoupled_weight_decay=self._decoupled)
+        super(Adam, self).__init__(params, defaults)
+        self.fused_steps = 0     # steps done as one ssp_adam_step launch
+        self.table_steps = 0     # steps done as one ssp_adam_step_table launch
+        self._lay = None         # the flat parameter / state buffers, the device table and what they were built for
+
+    def __setstate__(self, state):
+        super(Adam, self).__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault('amsgrad', False)
+            group.setdefault('decoupled_weight_decay', self._decoupled)
+            for name in ('maximize', 'capturable', 'differentiable', 'foreach', 'fused'):
+                if group.setdefault(name, None if name in ('foreach', 'fused') else False):
+                    raise ValueError("%s: a loaded group has %s=%r, which is not supported" % (self._name, name, group[name]))
+            for p in group['params']:
+                st = self.state.get(p, {})
+                if len(st) and not (torch.is_tensor(st['step']) and st['step'].device.type == 'cpu'):
+                    st['step'] = torch.tensor(float(st['step']), dtype=torch.float32)      # (a device tensor syncs here, once)
+
+    @property
+    def flat_numel(self):
+        """Floats of the flat parameter buffer the optimizer works on (0 before its first one-launch step)."""
+        return 0 if self._lay is None else self._lay['numel']
+
+    def _key(self, group, step):
+        if isinstance(group['lr'], torch.Tensor):
+            raise ValueError("%s: a tensor lr is not supported" % self._name)
+        return (float(group['lr']), float(group['betas'][0]), float(group['betas'][1]), float(group['eps']),
+                float(group['weight_decay']), bool(group['decoupled_weight_decay']), bool(group['amsgrad']), float(step))
+
+    def _init_state(self, p, group):
+        """torch's lazy state initialisation; the moment tensors become views of the flat buffers when a layout adopts them."""
+        state = self.state[p]
+        if len(state) == 0:
+            state['step'] = torch.tensor(0.0, dtype=torch.float32)
+            state['exp_avg'] = torch.zeros_like(p.data, memory_format=torch.preserve_format)
+            state['exp_avg_sq'] = torch.zeros_like(p.data, memory_format=torch.preserve_format)
+        if group['amsgrad'] and 'max_exp_avg_sq' not in state:
+            state['max_exp_avg_sq'] = torch.zeros_like(p.data, memory_format=torch.preserve_format)
+        return state
+
+    _STATE = (('m', 'exp_avg'), ('v', 'exp_avg_sq'), ('x', 'max_exp_avg_sq'))
+
+    def _ensure_layout(self, held, rows, any_ams):
+        """The flat buffers for these rows: kept while nothing moved, else (re-)adopted with every value copied in."""
+        lay = self._lay
+        key = (tuple(id(p) for p in held), tuple(map(tuple, rows)), bool(any_ams))
+        ok = lay is not None and lay['key'] == key
+        if ok:
+            for p, row in zip(held, rows):
+                st = self.state[p]
+                if p.data_ptr() != lay['p'].data_ptr() + 4 * row[0]:
+                    ok = False      # model.cuda() / load_state_dict replaced a tensor: adopt again (copies them in)
+                    break
+                for short, name in self._STATE:
+                    t = st.get(name)
+                    if t is not None and t.data_ptr() != lay[short].data_ptr() + 4 * row[2]:
+                        ok = False      # optimizer.load_state_dict() swapped the state tensors
+                        break
+                if not ok:
+                    break
+        if ok:
+            return lay
+        dev = held[0].device
+        numel = max(r[0] + (r[3] + 3) // 4 * 4 for r in rows)
+        bufs = dict(p=torch.zeros(numel, dtype=torch.float32, device=dev), m=torch.zeros(numel, dtype=torch.float32, device=dev),
+                    v=torch.zeros(numel, dtype=torch.float32, device=dev),
+                    x=torch.zeros(numel, dtype=torch.float32, device=dev) if any_ams else None)
+        for p, row in zip(held, rows):
+            pv = torch.as_strided(bufs['p'], p.shape, p.stride(), row[0])
+            pv.copy_(p.data)
+            p.data = pv
+            st = self.state[p]
+            for short, name in self._STATE:
+                old = st.get(name)
+                if old is None or bufs[short] is None:
+                    continue
+                sv = torch.as_strided(bufs[short], p.shape, p.stride(), row[2])
+                sv.copy_(old)
+                st[name] = sv
+        host = np.ascontiguousarray(np.asarray(rows, dtype=np.int64))
+        lay = self._lay = dict(key=key, numel=numel, host=host, dev=torch.from_numpy(host).to(dev), held=held, **bufs)
+        return lay
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        held, groups = [], []
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise RuntimeError("singleshotpose_amd.optim.%s runs on the MI355X HIP kernel only: parameter on %s"
+                                       % (self._name, p.device))
+                if p.grad.is_sparse:
+                    raise RuntimeError("%s does not support sparse gradients" % self._name)
+                self._init_state(p, group)
+                held.append(p)
+                groups.append(group)
+        if not held:
+            return loss
+        steps = [self.state[p]['step'] for p in held]
+        torch._foreach_add_(steps, 1)      # (CPU tensors: no device synchronisation; one dispatch for all of them)
+        gkey = {id(group): self._key(group, 0.0)[:7] for group in self.param_groups}
+        keys = [gkey[id(group)] + (s.item(),) for group, s in zip(groups, steps)]
+        st = torch.cuda.current_stream(held[0].device).cuda_stream
+        any_ams = any(k[6] for k in keys)
+        flat = SGD._flat_grads(held) if all(_dense(p.data) for p in held) else None
+        if flat is not None:
+            base, items, total = flat
+            g0 = held[0].grad
+            gbase = g0.data_ptr() - 4 * g0.storage_offset()
+            whole = (len(set(keys)) == 1 and len(held) == sum(len(g['params']) for g in self.param_groups) and
+                     sum((p.numel() + 3) // 4 * 4 for p in held) == total)
+            if whole:
+                # one range: parameters and state sit at the offsets of the gradient views
+                rows = [[off, off, off, p.numel(), 0] for p, off in items]
+                lay = self._ensure_layout(held, rows, any_ams)
+                h = _hyper9(keys[0])
+                _lib.call('ssp_adam_step', lay['p'].data_ptr(), gbase, lay['m'].data_ptr(), lay['v'].data_ptr(),
+                          lay['x'].data_ptr() if any_ams else None, total, *(h[:7] + (int(h[7]), int(h[8]), st)))
+                self.fused_steps += 1
+                weights_changed()      # raw-pointer writes do not bump tensor versions: invalidate packed-filter caches
+                return loss
+            built = build_adam_segment_table([(p.numel(), off, k) for (p, off), k in zip(items, keys)])
+            if built is not None:
+                rows, tkeys, numel = built
+                lay = self._ensure_layout(held, rows, any_ams)
+                hyper = (ctypes.c_double * (9 * len(tkeys)))(*[v for k in tkeys for v in _hyper9(k)])
+                _lib.call('ssp_adam_step_table', lay['p'].data_ptr(), gbase, lay['m'].data_ptr(), lay['v'].data_ptr(),
+                          lay['x'].data_ptr() if any_ams else None, numel, total, numel, lay['dev'].data_ptr(),
+                          lay['host'].ctypes.data, len(rows), ctypes.cast(hyper, ctypes.c_void_p), len(tkeys), st)
+                self.table_steps += 1
+                weights_changed()
+                return loss
+        # per-parameter launches of the same kernel: gradients that are no flat views, or more than 16 distinct tuples
+        for p, k in zip(held, keys):
+            g = p.grad
+            if not _dense(p.data):
+                raise RuntimeError("%s: parameter is neither contiguous nor channels-last" % self._name)
+            if g.dtype != torch.float32 or not _same_layout(g, p):
+                g = torch.empty_like(p.data).copy_(g)      # same memory order as the parameter
+            state = self.state[p]
+            ptrs = [p.data_ptr(), g.data_ptr(), state['exp_avg'].data_ptr(), state['exp_avg_sq'].data_ptr(),
+                    state['max_exp_avg_sq'].data_ptr() if k[6] else None]
+            if any(q is not None and q & 15 for q in ptrs):
+                raise RuntimeError("%s: parameter / gradient / state storage is not 16-byte aligned" % self._name)
+            for name in ('exp_avg', 'exp_avg_sq') + (('max_exp_avg_sq',) if k[6] else ()):
+                if not (state[name].is_cuda and state[name].dtype == torch.float32 and _same_layout(state[name], p)):
+                    raise RuntimeError("%s: state %s does not have the parameter's device, dtype and layout" % (self._name, name))
+            h = _hyper9(k)
+            _lib.call('ssp_adam_step', *(ptrs + [p.numel()] + list(h[:7]) + [int(h[7]), int(h[8]), st]))
+        weights_changed()
+        return loss
+
+
+class AdamW(Adam):
+    _decoupled = True
+    _name = 'AdamW'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None):
+        super(AdamW, self).__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize,
+                                    capturable=capturable, differentiable=differentiable, fused=fused)
+
+
+# ---- global-norm gradient clipping -------------------------------------------------------------------------------------
+_CLIP_GRID = 2048            # partials one table launch writes at most (include/ssp_hip.h)
+_CLIP_MAX_PARTIALS = 65536   # partials one ssp_grad_scale_table launch adds
+_clip_tables = {}            # (device, segments) -> (host rows, device rows): rebuilt only when the layout changes
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ for the 2-norm as two HIP launches (ssp_grad_sumsq_table, ssp_grad_scale_table)
+    with no host synchronisation: returns the total norm as a 0-dim device tensor.  Gradients that are views of one flat
+    buffer (what Plan.backward leaves) take one launch pair over a segment table; others one pair per tensor into one
+    partial array.  Works in front of optim.SGD and optim.Adam alike (the views stay views); in multi-GPU runs call it
+    after the reducer's all-reduce."""
+    if float(norm_type) != 2.0:
+        raise ValueError("clip_grad_norm_: norm_type=%r is not supported: only the 2-norm runs on the HIP kernels" % (norm_type,))
+    if foreach:
+        raise ValueError("clip_grad_norm_: foreach=%r is not supported" % (foreach,))
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    max_norm = float(max_norm)
+    if not params:
+        return torch.tensor(0.0)
+    for p in params:
+        g = p.grad
+        if not g.is_cuda:
+            raise RuntimeError("singleshotpose_amd.optim.clip_grad_norm_ runs on the MI355X HIP kernels only: gradient on %s" % g.device)
+        if g.dtype != torch.float32:
+            raise RuntimeError("clip_grad_norm_: gradient dtype %s (float32 only)" % g.dtype)
+    dev = params[0].grad.device
+    st = torch.cuda.current_stream(dev).cuda_stream
+    result = torch.empty(2, dtype=torch.float32, device=dev)
+    count = ctypes.c_int(0)
+    flat = SGD._flat_grads(params) if all(_dense(p.data) for p in params) else None
+    if flat is not None:
+        base, items, total = flat
+        segs = tuple((off, p.numel()) for p, off in items)
+        tab = _clip_tables.get((dev, segs))
+        if tab is None:
+            if len(_clip_tables) > 8:
+                _clip_tables.clear()
+            host = np.ascontiguousarray(np.asarray([[0, off, 0, n, 0] for off, n in segs], dtype=np.int64))
+            tab = _clip_tables[(dev, segs)] = (host, torch.from_numpy(host).to(dev))
+        host, table = tab
+        g0 = params[0].grad
+        gbase = g0.data_ptr() - 4 * g0.storage_offset()
+        partial = torch.empty(_CLIP_GRID, dtype=torch.float64, device=dev)
+        _lib.call('ssp_grad_sumsq_table', gbase, total, table.data_ptr(), host.ctypes.data, len(segs), partial.data_ptr(),
+                  _CLIP_GRID, ctypes.cast(ctypes.byref(count), ctypes.c_void_p), st)
+        _lib.call('ssp_grad_scale_table', gbase, total, table.data_ptr(), host.ctypes.data, len(segs), partial.data_ptr(),
+                  count.value, max_norm, result.data_ptr(), st)
+    else:
+        if len(params) > _CLIP_MAX_PARTIALS:
+            raise RuntimeError("clip_grad_norm_: more than %d separate gradient tensors" % _CLIP_MAX_PARTIALS)
+        for p in params:
+            g = p.grad
+            if not _dense(g) or g.data_ptr() & 15:
+                raise RuntimeError("clip_grad_norm_: a gradient is not dense in memory or not 16-byte aligned")
+        room = max(1, min(_CLIP_GRID, _CLIP_MAX_PARTIALS // len(params)))
+        partial = torch.empty(room * len(params), dtype=torch.float64, device=dev)
+        used = 0
+        for p in params:
+            _lib.call('ssp_grad_sumsq_table', p.grad.data_ptr(), p.grad.numel(), None, None, 1, partial.data_ptr() + 8 * used,
+                      room, ctypes.cast(ctypes.byref(count), ctypes.c_void_p), st)
+            used += count.value
+        for p in params:
+            _lib.call('ssp_grad_scale_table', p.grad.data_ptr(), p.grad.numel(), None, None, 1, partial.data_ptr(), used,
+                      max_norm, result.data_ptr(), st)
+    total_norm = result[0]
+    if error_if_nonfinite and not bool(torch.isfinite(total_norm)):
+        raise RuntimeError("The total norm of order %s for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`" % float(norm_type))
+    return total_norm
